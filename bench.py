@@ -23,10 +23,16 @@ run then also times the collective-free alternative — one model replica per GP
 own 64 prompts (`dp`, weak scaling) — and reports it as the extra object "dp_replicas"; `--parallelism
 dp` makes that the headline instead.
 
-Extra objects on the JSON line: "roofline" (dominant kernel, timed live with HIP events on
-the launch stream inside the timed region), "roofline_other" (the other hot kernels),
-"cpu_baseline" (oracle/cpu_port.c — the C restatement — timed on the host cores, rank 0,
-N=1 only), "ttft_p50_ms".
+A plain run does what the headline needs and no more: set-up, the warm-up jobs, the K timed jobs,
+the finiteness check of their outputs, the JSON line ("ttft_p50_ms" comes from events of the timed
+jobs themselves).  `--dump-outputs DIR` also writes what the last timed job computed as DIR/*.npy.
+
+`--full` adds every other measurement, each a run of its own around or after the timed region:
+"roofline" (dominant kernel, timed live with HIP events on the launch stream inside the timed region;
+the decode kernels from HIP-graph replays afterwards), "roofline_other" (the other hot kernels, with
+the prefill GEMM without its weight image), "plugin_surface" (the same job through the plain op
+surface, N = 1), "dp_replicas" / "baseline_tp8_model" (N > 1), "cpu_baseline" (oracle/cpu_port.c —
+the C restatement — timed on the host cores, rank 0, N = 1 only).
 """
 from __future__ import annotations
 
@@ -60,7 +66,16 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--quant", default=None, choices=["awq", "gptq", "fp8", "int8", "none"],
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel roofline figures, the prefill GEMM "
+                         "without its weight image, the plugin-surface jobs, the dp / TP=8 extras of multi-GPU runs and "
+                         "the CPU baseline (each can still be switched off by its own --no-* / --skip-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed job computed (every sequence's first "
+                         "token, the last prefill chunk's logits, the last decode step's logits, the final tokens and "
+                         "positions) as DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed seeded sample "
+                         "of a larger array)")
+    ap.add_argument("--quant",default=None, choices=["awq", "gptq", "fp8", "int8", "none"],
                     help="weight format; default: the one BASELINE.json names for the model (llama-3-8b: awq, "
                          "llama-3-70b: fp8, qwen2-72b: gptq)")
     ap.add_argument("--model", default="llama-3-8b", choices=sorted(MODELS),
@@ -99,8 +114,10 @@ def parse_args():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--kernel-stats", action="store_true",
-                    help="print the per-kernel event timings table to stderr")
-    return ap.parse_args()
+                    help="print the per-kernel event timings table to stderr (implies --full)")
+    args = ap.parse_args()
+    args.full = args.full or args.kernel_stats
+    return args
 
 
 class EventTimer:
@@ -306,6 +323,7 @@ def run_job(model, tokens, args, timer=None, ttft=None):
     model.set_decode_lengths(torch.full((B,), Lin, device=model.device))
     for _ in range(Lout - 1):
         model.decode_step(use_graph=not args.no_graph)
+    model.job_first_tokens = first       # (kept for --dump-outputs: the tensor itself, no extra launch)
 
 
 def cpu_baseline(args, cfg):
@@ -480,6 +498,39 @@ def check_outputs(model, what: str) -> None:
         raise SystemExit(f"bench.py: {what}: sampled tokens outside the vocabulary")
 
 
+DUMP_LIMIT_BYTES = 63 * 1000 * 1000      # array bytes; the .npy headers stay well inside the 64 MB of the option
+
+
+def dump_outputs(model, out_dir: str) -> dict:
+    """What a caller of the timed path holds after the last timed job, as out_dir/<name>.npy: the first token of
+    every sequence (prefill), the logits of the last prefill chunk and of the last decode step, the tokens the last
+    decode step sampled and the positions it advanced to.  Logits as float32 (exact from bf16 / fp16), integers as
+    float64 (exact).  An array that would take the total past 64 MB is stored as a fixed sample: the elements at
+    the sorted flat indices numpy's default_rng(0) draws without replacement (the same for every run of a shape).
+    Returns {name: {"shape", "stored"}} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [("first_tokens", model.job_first_tokens, np.float64),
+              ("final_tokens", model.d_tokens, np.float64),
+              ("final_positions", model.d_positions, np.float64),
+              ("last_prefill_logits", getattr(model, "last_prefill_logits", None), np.float32),
+              ("last_decode_logits", getattr(model, "last_logits", None), np.float32)]
+    left, info = DUMP_LIMIT_BYTES, {}
+    for name, t, dt in arrays:
+        if t is None:
+            continue
+        a = t.detach().to("cpu", torch.float64 if dt is np.float64 else torch.float32).numpy()
+        stored = a.size
+        if a.nbytes > left:
+            stored = left // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=stored, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": list(t.shape), "stored": int(stored)}
+    return info
+
+
 def decode_kernel_times(model, timer: EventTimer, args, reps: int = 3):
     """Graph-consistent timings of the decode step's kernels.  One eager decode step is run with the timer in
     collect mode (it records every wrapped launch as a closure over that step's real tensors); then, per kernel
@@ -585,6 +636,79 @@ def hbm_weights_gb(model) -> dict:
             "embed_lm_head": round(other / 1e9, 3), "total": round((w + img + other) / 1e9, 3)}
 
 
+def roofline_entries(model, timer, args, elapsed, quant, tp, world, rank):
+    """--full: the per-kernel entries of "roofline" / "roofline_other", sorted by their share of the job."""
+    from vllm_metax_amd import harness
+    agg = timer.summary()
+    dec = decode_kernel_times(model, timer, args)
+    dec_named = {}
+    for name, d in dec.items():  # decode launches: graph-consistent timings, beside the prefill-side entries
+        final = name if name not in agg else name + "_decode"
+        agg[final] = d
+        dec_named[final] = d
+
+    def roof(name, d):
+        avg_ms = d["ms"] / d["launches"]
+        extra = {"timing": d["timing"]} if "timing" in d else {}
+        if d["flops"] > 0 and name.endswith("large_m") or name == "paged_prefill_attention":
+            ach = d["flops"] / d["launches"] / (avg_ms * 1e-3) / 1e12
+            peak = MFMA_8BIT_PEAK_TFLOPS if name.startswith(("fp8_gemm", "int8_gemm")) \
+                else MFMA_BF16_PEAK_TFLOPS
+            r = {"kernel": name, "bound": "mfma", "achieved": round(ach, 2),
+                 "peak": peak, "unit": "TFLOP/s",
+                 "frac": round(ach / peak, 4), "traffic": None,
+                 "avg_launch_us": round(avg_ms * 1e3, 2), "launches": d["launches"],
+                 "total_ms": round(d["ms"], 2), **extra}
+            if name.endswith("gemm_large_m"):
+                # north_star words its GEMM target against the fp8 MFMA peak (5 PFLOP/s dense); the
+                # w4a16 GEMM multiplies bf16 operands, so `frac` is against the bf16 peak and this
+                # field restates the same rate against the fp8 peak (SURVEY §8d asks for both)
+                r["frac_fp8_peak"] = round(ach / MFMA_8BIT_PEAK_TFLOPS, 4)
+            return r
+        ach = d["bytes"] / d["launches"] / (avg_ms * 1e-3) / 1e9
+        return {"kernel": name, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                "avg_launch_us": round(avg_ms * 1e3, 2), "launches": d["launches"],
+                "total_ms": round(d["ms"], 2), **extra}
+
+    # ranking by the share of the JOB: a prefill kernel's events cover the K timed jobs, a decode kernel's graph
+    # timing covers `reps` steps — scale the latter to the decode steps of the K jobs before sorting
+    def job_ms(name, d):
+        if name in dec_named:
+            return d["ms"] / d["steps_timed"] * (args.output_len - 1) * args.steps
+        return d["ms"]
+    roofs = []
+    for n_, d in agg.items():
+        r = roof(n_, d)
+        r["job_share"] = round(job_ms(n_, d) / (elapsed * 1e3), 4)
+        roofs.append(r)
+    roofs.sort(key=lambda r: -r["job_share"])
+    # HBM-side bytes per launch from the committed PMC passes (separate rocprofv3 --pmc runs of
+    # the same kernels at the same shapes; a counter pass cannot run inside the timed region)
+    here = os.path.dirname(os.path.abspath(__file__))
+    tpath = next((pth for pth in (os.path.join(here, "profiles", f) for f in ("r03_pmc_traffic.json",
+                                                                              "r02_pmc_traffic.json"))
+                  if os.path.exists(pth)), None)
+    if tpath and args.model == "llama-3-8b" and tp == 1 and args.kv_cache_dtype == "auto" and quant == "awq":
+        with open(tpath) as f:
+            traffic = json.load(f)
+        for r in roofs:
+            if r["kernel"] in traffic:
+                r["traffic"] = traffic[r["kernel"]]
+                r["traffic_unit"] = f"bytes per launch (2*FETCH_SIZE + WRITE_SIZE, profiles/{os.path.basename(tpath)})"
+    if quant in ("awq", "gptq") and harness.QLinear.prepack and world == 1 and not args.tp_rank_of:
+        try:
+            e = no_prepack_entry(model, args, timer)
+            if e is not None:
+                roofs.append(e)
+        except Exception as ex:  # noqa: BLE001
+            print(f"bench.py: no-prepack entry failed: {ex!r}", file=sys.stderr)
+    if args.kernel_stats and rank == 0:
+        for r in roofs:
+            print(json.dumps(r), file=sys.stderr)
+    return roofs
+
+
 def make_cfg(args, tp_degree, rank, model_name=None, quant=None):
     from vllm_metax_amd import harness
     name = model_name or args.model
@@ -661,86 +785,25 @@ def main():
     # every hot op is wrapped so that a launch CAN be bracketed by HIP events; the timer is off during warm-up /
     # graph capture and on inside the timed region, where it sees the eagerly launched kernels (all of prefill);
     # the graph-replayed decode launches are timed afterwards, again from HIP graphs (decode_kernel_times).
-    timer = EventTimer()
-    instrument(model, timer)
+    # A plain run leaves the ops unwrapped: its timed region holds the job's own launches and nothing else.
+    timer = None
+    if args.full:
+        timer = EventTimer()
+        instrument(model, timer)
     # ---- timed region: exactly K jobs -------------------------------------------------
     elapsed, ttfts = timed_jobs(model, tokens, args, world, barrier, timer)
     ttft_p50 = statistics.median(ttfts) if ttfts else None
     check_outputs(model, f"{cfg.name} {quant}")
+    dumped = dump_outputs(model, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     graph_ok, graph_err = model._graph not in (None, False), model.graph_error
     weights_gb = hbm_weights_gb(model)
 
-    agg = timer.summary()
-    dec = decode_kernel_times(model, timer, args)
-    dec_named = {}
-    for name, d in dec.items():  # decode launches: graph-consistent timings, beside the prefill-side entries
-        final = name if name not in agg else name + "_decode"
-        agg[final] = d
-        dec_named[final] = d
-
-    def roof(name, d):
-        avg_ms = d["ms"] / d["launches"]
-        extra = {"timing": d["timing"]} if "timing" in d else {}
-        if d["flops"] > 0 and name.endswith("large_m") or name == "paged_prefill_attention":
-            ach = d["flops"] / d["launches"] / (avg_ms * 1e-3) / 1e12
-            peak = MFMA_8BIT_PEAK_TFLOPS if name.startswith(("fp8_gemm", "int8_gemm")) \
-                else MFMA_BF16_PEAK_TFLOPS
-            r = {"kernel": name, "bound": "mfma", "achieved": round(ach, 2),
-                 "peak": peak, "unit": "TFLOP/s",
-                 "frac": round(ach / peak, 4), "traffic": None,
-                 "avg_launch_us": round(avg_ms * 1e3, 2), "launches": d["launches"],
-                 "total_ms": round(d["ms"], 2), **extra}
-            if name.endswith("gemm_large_m"):
-                # north_star words its GEMM target against the fp8 MFMA peak (5 PFLOP/s dense); the
-                # w4a16 GEMM multiplies bf16 operands, so `frac` is against the bf16 peak and this
-                # field restates the same rate against the fp8 peak (SURVEY §8d asks for both)
-                r["frac_fp8_peak"] = round(ach / MFMA_8BIT_PEAK_TFLOPS, 4)
-            return r
-        ach = d["bytes"] / d["launches"] / (avg_ms * 1e-3) / 1e9
-        return {"kernel": name, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                "avg_launch_us": round(avg_ms * 1e3, 2), "launches": d["launches"],
-                "total_ms": round(d["ms"], 2), **extra}
-
-    # ranking by the share of the JOB: a prefill kernel's events cover the K timed jobs, a decode kernel's graph
-    # timing covers `reps` steps — scale the latter to the decode steps of the K jobs before sorting
-    def job_ms(name, d):
-        if name in dec_named:
-            return d["ms"] / d["steps_timed"] * (args.output_len - 1) * args.steps
-        return d["ms"]
-    roofs = []
-    for n_, d in agg.items():
-        r = roof(n_, d)
-        r["job_share"] = round(job_ms(n_, d) / (elapsed * 1e3), 4)
-        roofs.append(r)
-    roofs.sort(key=lambda r: -r["job_share"])
-    # HBM-side bytes per launch from the committed PMC passes (separate rocprofv3 --pmc runs of
-    # the same kernels at the same shapes; a counter pass cannot run inside the timed region)
-    here = os.path.dirname(os.path.abspath(__file__))
-    tpath = next((pth for pth in (os.path.join(here, "profiles", f) for f in ("r03_pmc_traffic.json",
-                                                                              "r02_pmc_traffic.json"))
-                  if os.path.exists(pth)), None)
-    if tpath and args.model == "llama-3-8b" and tp == 1 and args.kv_cache_dtype == "auto" and quant == "awq":
-        with open(tpath) as f:
-            traffic = json.load(f)
-        for r in roofs:
-            if r["kernel"] in traffic:
-                r["traffic"] = traffic[r["kernel"]]
-                r["traffic_unit"] = f"bytes per launch (2*FETCH_SIZE + WRITE_SIZE, profiles/{os.path.basename(tpath)})"
-    if quant in ("awq", "gptq") and harness.QLinear.prepack and world == 1 and not args.tp_rank_of:
-        try:
-            e = no_prepack_entry(model, args, timer)
-            if e is not None:
-                roofs.append(e)
-        except Exception as ex:  # noqa: BLE001
-            print(f"bench.py: no-prepack entry failed: {ex!r}", file=sys.stderr)
-    if args.kernel_stats and rank == 0:
-        for r in roofs:
-            print(json.dumps(r), file=sys.stderr)
+    # ---- everything below, up to the result line, is --full's: measurements beside the headline ----
+    roofs = roofline_entries(model, timer, args, elapsed, quant, tp, world, rank) if args.full else []
 
     # ---- tp runs: the collective-free alternative (one replica per GPU) measured in the same run ----
     dp_extra = None
-    if tp > 1 and world > 1 and not args.no_dp_extra and args.model == "llama-3-8b":
+    if args.full and tp > 1 and world > 1 and not args.no_dp_extra and args.model == "llama-3-8b":
         del model
         torch.cuda.empty_cache()
         rep_model = harness.HotPathModel(make_cfg(args, 1, 0), args.batch, max_len, device=f"cuda:{local_rank}", seed=0)
@@ -757,7 +820,7 @@ def main():
 
     # ---- --gpus 8, default model: BASELINE's TP=8 headline model (Llama-3-70B FP8) in the same run ----
     tp8_extra = None
-    if world == 8 and tp == 8 and args.model == "llama-3-8b" and not args.no_tp8_extra:
+    if args.full and world == 8 and tp == 8 and args.model == "llama-3-8b" and not args.no_tp8_extra:
         model = None
         torch.cuda.empty_cache()
         try:
@@ -781,7 +844,7 @@ def main():
 
     # ---- N = 1: the same job through the plain op surface upstream vLLM reaches (no cross-op fusion) ----
     surface = None
-    if world == 1 and not args.tp_rank_of and not args.no_plugin_surface:
+    if args.full and world == 1 and not args.tp_rank_of and not args.no_plugin_surface:
         model = None
         torch.cuda.empty_cache()
         try:
@@ -845,6 +908,7 @@ def main():
         "value": round(out_tokens / elapsed, 2),
         "unit": "output tokens/s",
         "n_gpus": world,
+        "full": bool(args.full),
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -892,7 +956,9 @@ def main():
         result["baseline_tp8_model"] = tp8_extra
     if surface is not None:
         result["plugin_surface"] = surface
-    if world == 1 and not args.skip_cpu and not args.tp_rank_of:
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    if args.full and world == 1 and not args.skip_cpu and not args.tp_rank_of:
         try:
             result["cpu_baseline"] = cpu_baseline(args, cfg)
         except Exception as e:  # the baseline must never take the GPU number down with it
