@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MI355X_ABI_VERSION 5   /* 5: + paged_attention_v2_ps, scaled_mm_fp8_deferred and its slab consumers, scaled_mm_prepack(ed), scaled_mm_split_elems, w4a16_prepacked_split_elems (additive; w4a16_gemm_prepacked takes m >= 384); 4: + paged_prefill_attention_alibi, silu_and_mul_per_token_quant (additive); 3: + greedy_advance, paged_attention_fused_qkv, *_rms_norm_image, paged_prefill_attention_image (additive);
+#define MI355X_ABI_VERSION 6   /* 6: + w4a16_last_route and the MI355X_W4_ROUTE_* bits (additive, host-side diagnostic); 5: + paged_attention_v2_ps, scaled_mm_fp8_deferred and its slab consumers, scaled_mm_prepack(ed), scaled_mm_split_elems, w4a16_prepacked_split_elems (additive; w4a16_gemm_prepacked takes m >= 384); 4: + paged_prefill_attention_alibi, silu_and_mul_per_token_quant (additive); 3: + greedy_advance, paged_attention_fused_qkv, *_rms_norm_image, paged_prefill_attention_image (additive);
                                 * 2 was BREAKING (kv_cache_dtype / k_scale / v_scale inserted before `stream` in reshape_and_cache*,
                                 * paged_attention_v1/_v2, paged_prefill_attention): a binding must refuse a library whose
                                 * mi355x_abi_version() differs from the version it was written for (vllm_metax_amd/_abi.py does) */
@@ -327,8 +327,9 @@ int mi355x_awq_dequantize(void* out, const uint32_t* qweight, const void* scales
  * depend on timing).  8*m*n elements allow every split the planner wants.  It need not be
  * zeroed; contents on exit are unspecified.
  * `dq_workspace` (16-byte aligned, may be NULL) is scratch for re-tiled operands:
- *   - M <= 64: >= roundup(m,16)*k*2 bytes: the activations are re-tiled into MFMA operand
- *     images, which selects the LDS-DMA "stripe" decode kernel (k % 128 == 0, group 32/64/128k);
+ *   - M <= 64: >= roundup(m,16)*k*2 bytes (64*k*2 for 33..48 rows: the kernel runs 1, 2 or 4 row
+ *     tiles and reads an image of as many): shapes the LDS-DMA "stripe" decode kernel does not take
+ *     (it wants k % 128 == 0, group 32/64/128k) have their activations re-tiled into MFMA operand images;
  *   - M >= 1024: >= (n + roundup(m,16))*k*2 bytes: weights are dequantised once and
  *     activations re-tiled, then a pure-MFMA GEMM follows (same numerics).
  *   Without it the register-staged kernels are used.  Contents on exit are unspecified.
@@ -413,6 +414,22 @@ int64_t mi355x_w4a16_prepacked_split_elems(int m, int n, int k);
 int mi355x_w4a16_gemm_prepacked(void* out, const void* a, const void* image, void* a_workspace,
                                 int64_t a_workspace_bytes, int m, int n, int k, int64_t lda, int mode,
                                 int dtype, mi355x_stream stream);
+
+/* Host-side diagnostic: the kernels launched by the most recent w4a16 GEMM entry (mi355x_awq_gemm*,
+ * mi355x_gptq_gemm, mi355x_w4a16_gemm_prepacked) on the calling thread, as a mask of the bits below; 0 before any
+ * such call.  Every entry clears the mask first; an entry that fails leaves the launches it had made.  The tests
+ * assert the route of every shape with it, so that a change of the router cannot orphan a kernel unnoticed. */
+enum {
+  MI355X_W4_ROUTE_STRIPE = 1,      /* w4a16_gemm_stripe_kernel (w4a16_stripe.hip)                              */
+  MI355X_W4_ROUTE_SMALL_M = 2,     /* w4a16_gemm_small_m_kernel (w4a16.hip)                                    */
+  MI355X_W4_ROUTE_LARGE_M = 4,     /* w4a16_gemm_large_m_kernel, the 128 x 256 tile kernel (w4a16_large.hip)   */
+  MI355X_W4_ROUTE_IMAGE = 8,       /* gemm_packed_kernel on operand images, per call or prepacked (w4a16_unfused.hip) */
+  MI355X_W4_ROUTE_ANY_N4 = 16,     /* w4a16_gemm_any_n_kernel (n % 64 != 0)                                    */
+  MI355X_W4_ROUTE_ANY_8 = 32,      /* w8a16_gemm_any_kernel (8-bit GPTQ below 1024 rows)                       */
+  MI355X_W4_ROUTE_PACK_A = 64,     /* pack_a_kernel: activations re-tiled into operand images first            */
+  MI355X_W4_ROUTE_SUM_SLABS = 128  /* K was split: fp32 slabs added by w4a16_sum_slabs(_silu)_kernel           */
+};
+int mi355x_w4a16_last_route(void);
 
 /* gptq_gemm: C = A[:, perm] . ((Q - (Z + 1)) * S), 4-bit, shuffled layout.
  * g_idx == NULL => no act-order; else g_idx is the argsort permutation and

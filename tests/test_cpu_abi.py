@@ -33,7 +33,7 @@ def test_header_declares_expected_entry_points():
                    "mi355x_gptq_shuffle", "mi355x_awq_dequantize", "mi355x_scaled_mm_fp8",
                    "mi355x_rms_norm", "mi355x_fused_add_rms_norm", "mi355x_rotary_embedding",
                    "mi355x_rms_norm_static_fp8_quant", "mi355x_rms_norm_dynamic_per_token_quant",
-                   "mi355x_static_scaled_fp8_quant", "mi355x_silu_and_mul"]:
+                   "mi355x_static_scaled_fp8_quant", "mi355x_silu_and_mul", "mi355x_w4a16_last_route"]:
         assert needed in syms
 
 
@@ -43,7 +43,7 @@ def test_library_exports_every_declared_symbol(built):
         assert hasattr(lib, sym), f"{sym} declared in the header but not exported"
     # and the ctypes prototype table covers exactly the header
     assert sorted(built.PROTOTYPES) == header_symbols()
-    assert lib.mi355x_abi_version() == built.ABI_VERSION == 5
+    assert lib.mi355x_abi_version() == built.ABI_VERSION == 6
 
 
 def test_argument_errors_surface_without_a_gpu(built):
@@ -57,6 +57,7 @@ def test_argument_errors_surface_without_a_gpu(built):
     assert rc == -1 or "kv cache" in built.last_error()
     rc = lib.mi355x_awq_gemm(None, None, None, None, None, None, 0, None, 0, 4, 100, 512, 128, 512, built.BF16, None)
     assert rc == -2 and "multiple of 8" in built.last_error()
+    assert lib.mi355x_w4a16_last_route() == 0   # nothing was launched
     # v1 keeps the logits of a whole sequence in LDS: the limit the backend's v1 / v2 choice uses
     assert lib.mi355x_paged_attention_v1_max_seq_len(64, 32, 8, 128, 16, built.BF16) == 6656
     assert lib.mi355x_paged_attention_v1_max_seq_len(64, 32, 8, 128, 16, built.F32) == 4928

@@ -177,14 +177,22 @@ def test_gptq_gemm_qwen2_72b_tp8_shapes():
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("m,k,n", [(128, 4096, 512), (1000, 1024, 1280), (2048, 4096, 6144), (513, 14336, 256)])
 def test_awq_gemm_prefill_shapes(dtype, m, k, n):
-    """Prefill-sized M (the 128 x 256 MFMA tile kernel), incl. ragged M and N % 256 != 0."""
+    """Prefill-sized M, incl. ragged M and N % 256 != 0.  These are stripe shapes (k % 128 == 0, group 128): below
+    1024 rows they run as passes of up to 128 rows through the stripe kernel (K split through slabs in the dequant
+    scratch where the stripes alone leave the chip idle: not the 10 stripes x 8 stages of 1024 x 1280); from 1024 rows
+    through the operand-image GEMM.  (The 128 x 256 MFMA tile kernel, which served them before the 128-row stripe
+    passes, is covered by tests/test_gpu_w4a16_routes.py.)  The route is asserted."""
     group = 128
+    O = ops()
+    route = {128: O.W4_ROUTE_STRIPE | O.W4_ROUTE_SUM_SLABS, 1000: O.W4_ROUTE_STRIPE,
+             2048: O.W4_ROUTE_IMAGE | O.W4_ROUTE_PACK_A, 513: O.W4_ROUTE_STRIPE | O.W4_ROUTE_SUM_SLABS}[m]
     qw, qz, sc, _, _ = make_awq(k, n, group, dtype, seed=14)
     x = (torch.randn(m, k, generator=torch.Generator().manual_seed(15)) * 0.5).to(dtype)
     ref = R.awq_gemm(x, R.awq_to_gptq_4bit(qw), sc, qz)
     d = dev()
     q2d = ops().awq_to_gptq_4bit(qw.to(d))
     out = ops().awq_gemm(x.to(d), q2d, qz.to(d), sc.to(d), 8, torch.empty(0), dtype == torch.bfloat16)
+    assert O.w4a16_last_route() == route, f"prefill {m}x{k}x{n}: route {O.w4a16_last_route()}, expected {route}"
     _check_gemm(out, ref, f"awq_gemm prefill {m}x{k}x{n}")
 
 

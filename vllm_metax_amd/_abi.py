@@ -16,7 +16,7 @@ LIB_PATH = PKG_DIR / "libmi355x_hotpath.so"
 
 F16, BF16, F32 = 0, 1, 2
 KV_AUTO, KV_FP8_E4M3, KV_FP8_E5M2 = 0, 1, 2          # mi355x_kv_cache_dtype
-ABI_VERSION = 5                      # the MI355X_ABI_VERSION the PROTOTYPES below were written for
+ABI_VERSION = 6                    # the MI355X_ABI_VERSION the PROTOTYPES below were written for
 
 _P = c_void_p
 _I = c_int
@@ -82,6 +82,7 @@ PROTOTYPES = {
     "mi355x_w4a16_prepack": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mi355x_w4a16_gemm_prepacked": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _L, _I, _I, _P]),
     "mi355x_w4a16_prepacked_split_elems": (_L, [_I, _I, _I]),
+    "mi355x_w4a16_last_route": (_I, []),
     "mi355x_gptq_shuffle": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "mi355x_gptq_gemm": (
         _I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _P]),

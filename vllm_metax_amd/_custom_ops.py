@@ -630,13 +630,25 @@ def _dq_scratch(m: int, n: int, k: int, device) -> Optional[torch.Tensor]:
     grown to the largest n*k seen; the kernels of one stream run in order, so sharing is safe)."""
     m_pad = (m + 15) // 16 * 16
     if m <= 64:
-        need = m_pad * k * 2                    # decode: packed activations only
+        # decode: packed activations only, as many 16-row tiles as the kernel variant reads (1, 2 or 4)
+        need = (16 if m <= 16 else 32 if m <= 32 else 64) * k * 2
     elif m < 1024:
         need = 8 * 128 * n * 4                  # 64 < m < 1024: fp32 split-K slabs of one 128-row pass
     else:
         # prefill: packed weights + packed activations + the partial tiles of a K split (few 256 x 256 tiles)
         need = ((n + m_pad) * k * 2 + 15) // 16 * 16 + 4 * int(_abi.load().mi355x_w4a16_prepacked_split_elems(m, n, k))
     return _grow(_DQ_SCRATCH, device, need, torch.uint8)
+
+
+# MI355X_W4_ROUTE_* (include/mi355x_hotpath.h): the bits of w4a16_last_route()
+W4_ROUTE_STRIPE, W4_ROUTE_SMALL_M, W4_ROUTE_LARGE_M, W4_ROUTE_IMAGE = 1, 2, 4, 8
+W4_ROUTE_ANY_N4, W4_ROUTE_ANY_8, W4_ROUTE_PACK_A, W4_ROUTE_SUM_SLABS = 16, 32, 64, 128
+
+
+def w4a16_last_route() -> int:
+    """Mask of the kernels the most recent w4a16 GEMM call of this thread launched (awq_gemm*, gptq_gemm,
+    w4a16_gemm_prepacked); 0 before any.  A host-side diagnostic for the tests, which assert every shape's route."""
+    return int(_abi.load().mi355x_w4a16_last_route())
 
 
 def awq_to_gptq_4bit(qweight: torch.Tensor) -> torch.Tensor:

@@ -118,6 +118,11 @@ __device__ __forceinline__ uint4 dequant_word_fp8pk(uint32_t w, float s512, floa
 
 enum ZeroMode { kZeroAwq = 0, kZeroGptq = 1 };
 
+// mi355x_w4a16_last_route: the kernels the current w4a16 GEMM entry launched (MI355X_W4_ROUTE_* bits; defined in
+// w4a16.hip).  Host-side bookkeeping only: every entry clears it, every launch site ORs its bit in.
+extern thread_local int w4_route_mask;
+inline void w4_route_note(int bits) { w4_route_mask |= bits; }
+
 // zero points of the 4 columns n .. n+3 (n % 4 == 0) from their packed word
 template <int ZMODE>
 __device__ __forceinline__ void unpack_zeros4(uint32_t w, int n, float (&z)[4]) {

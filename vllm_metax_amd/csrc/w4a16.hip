@@ -26,6 +26,8 @@
 
 namespace mi355x {
 
+thread_local int w4_route_mask = 0;
+
 // ------------------------------------------------------------------ repack / shuffle
 
 // One thread per (k-block of 8 rows, word column): reads 8 AWQ words (rows 8kk..8kk+7 of
@@ -352,6 +354,7 @@ static int launch_small_m(const GemmArgs& g, int row0, int rows) {
   sk = (total_steps + steps_per_split - 1) / steps_per_split;
   float* ws = g.ws;
   const int mt = (rows + 15) / 16;
+  const int mtv = mt <= 1 ? 1 : (mt <= 2 ? 2 : 4);   // row tiles of the kernel variant (3 tiles run as 4)
   int group_shift = -1;  // log2(group) when group is a power of two (avoids an integer division)
   if ((g.group & (g.group - 1)) == 0) {
     group_shift = 0;
@@ -359,12 +362,14 @@ static int launch_small_m(const GemmArgs& g, int row0, int rows) {
   }
   // optional: re-tile the activations into MFMA operand images first (one tiny launch)
   const uint4* a_packed = nullptr;
-  const int64_t pack_bytes = (int64_t)mt * 16 * g.k * 2;
+  // the image has every tile the kernel reads: MT of them, the tiles past `rows` zero (pack_a_kernel)
+  const int64_t pack_bytes = (int64_t)mtv * 16 * g.k * 2;
   if (g.dq_ws != nullptr && g.dq_ws_bytes >= pack_bytes && g.k % 32 == 0) {
-    hipLaunchKernelGGL(pack_a_kernel<T>, dim3((g.k + kPackK - 1) / kPackK, mt), dim3(256), 0, g.stream,
+    hipLaunchKernelGGL(pack_a_kernel<T>, dim3((g.k + kPackK - 1) / kPackK, mtv), dim3(256), 0, g.stream,
                        static_cast<T*>(g.dq_ws), a, rows, g.k, g.lda);
     int prc = check_launch("pack_a(small)");
     if (prc) return prc;
+    w4_route_note(MI355X_W4_ROUTE_PACK_A);
     a_packed = static_cast<const uint4*>(g.dq_ws);
   }
   dim3 grid(col_tiles, sk), block(kSmThreads);
@@ -383,19 +388,21 @@ static int launch_small_m(const GemmArgs& g, int row0, int rows) {
     if (group_shift >= 0) LAUNCH_SM2(MTV, true); \
     else LAUNCH_SM2(MTV, false);            \
   } while (0)
-  if (mt <= 1) LAUNCH_SM(1);
-  else if (mt <= 2) LAUNCH_SM(2);
+  if (mtv == 1) LAUNCH_SM(1);
+  else if (mtv == 2) LAUNCH_SM(2);
   else LAUNCH_SM(4);
 #undef LAUNCH_SM3
 #undef LAUNCH_SM2
 #undef LAUNCH_SM
   int rc = check_launch("w4a16_gemm_small_m");
   if (rc) return rc;
+  w4_route_note(MI355X_W4_ROUTE_SMALL_M);
   if (sk > 1) {
     const int64_t n4 = (int64_t)rows * g.n / 4;
     hipLaunchKernelGGL(w4a16_sum_slabs_kernel<T>, dim3((n4 + 255) / 256), dim3(256), 0, g.stream, c,
                        ws, n4, sk);
     rc = check_launch("w4a16_sum_slabs");
+    w4_route_note(MI355X_W4_ROUTE_SUM_SLABS);
   }
   return rc;
 }
@@ -512,6 +519,7 @@ static int launch_any_n(const GemmArgs& g) {
     hipLaunchKernelGGL(w8a16_gemm_any_kernel<T>, grid8, block8, 0, g.stream, static_cast<T*>(g.c),
                        static_cast<const T*>(g.a), g.qw, static_cast<const T*>(g.scales), g.qz, g.m, g.n,
                        g.k, g.group, g.lda);
+    w4_route_note(MI355X_W4_ROUTE_ANY_8);
     return check_launch("w8a16_gemm_any");
   }
   dim3 grid((g.n + 15) / 16, (g.m + 7) / 8), block(256);
@@ -524,6 +532,7 @@ static int launch_any_n(const GemmArgs& g) {
                        static_cast<T*>(g.c), static_cast<const T*>(g.a), g.qw,
                        static_cast<const T*>(g.scales), g.qz, g.m, g.n, g.k, g.group, g.lda);
   }
+  w4_route_note(MI355X_W4_ROUTE_ANY_N4);
   return check_launch("w4a16_gemm_any_n");
 }
 
@@ -554,6 +563,20 @@ static int run_gemm_t(const GemmArgs& g, int dtype) {
     gm.ws = static_cast<float*>(g.dq_ws);
     gm.ws_elems = g.dq_ws_bytes / 4;
   }
+  // The 64-row halves below go to the small-M kernel, which packs its activations at the START of the same scratch
+  // (up to 4 row tiles: 64 * k * 2 bytes) and reads them while other workgroups already store their slabs: slabs
+  // aliased onto the scratch go BEHIND that image, or K is not split where the scratch has no room for both.
+  GemmArgs gh = gm;
+  if (gm.ws != g.ws) {
+    const int64_t image_bytes = (int64_t)64 * g.k * 2;   // a multiple of 16 (k % 32 == 0)
+    if (g.dq_ws_bytes > image_bytes) {
+      gh.ws = reinterpret_cast<float*>(static_cast<char*>(g.dq_ws) + image_bytes);
+      gh.ws_elems = (g.dq_ws_bytes - image_bytes) / 4;
+    } else {
+      gh.ws = nullptr;
+      gh.ws_elems = 0;
+    }
+  }
   const int pass = g.m > 64 ? 128 : 64;
   bool stripe_ok = true;
   if (g.m >= 128) {
@@ -572,7 +595,7 @@ static int run_gemm_t(const GemmArgs& g, int dtype) {
         const int rr = (row0 + rows - r1) < 64 ? (row0 + rows - r1) : 64;
         rc = w4a16_gemm_stripe_dispatch(gm, dtype, r1, rr);
         if (rc == 1)
-          rc = g.zmode == kZeroAwq ? launch_small_m<T, kZeroAwq>(gm, r1, rr) : launch_small_m<T, kZeroGptq>(gm, r1, rr);
+          rc = g.zmode == kZeroAwq ? launch_small_m<T, kZeroAwq>(gh, r1, rr) : launch_small_m<T, kZeroGptq>(gh, r1, rr);
         if (rc) return rc;
       }
       continue;
@@ -675,6 +698,7 @@ int mi355x_awq_gemm(void* c, const void* a, const uint32_t* qweight, const void*
                     const uint32_t* qzeros, float* workspace, int64_t workspace_elems,
                     void* dq_workspace, int64_t dq_workspace_bytes, int m, int n, int k,
                     int group_size, int64_t lda, int dtype, mi355x_stream stream) {
+  w4_route_mask = 0;
   GemmArgs g{c, a, qweight, scales, qzeros, workspace, workspace_elems, dq_workspace,
              dq_workspace_bytes, m, n, k, group_size, lda, kZeroAwq,
              static_cast<hipStream_t>(stream)};
@@ -688,6 +712,7 @@ int mi355x_awq_gemm_deferred(void* c, const void* a, const uint32_t* qweight, co
                              void* dq_workspace, int64_t dq_workspace_bytes, int m, int n, int k,
                              int group_size, int64_t lda, int dtype, int* sk_out,
                              mi355x_stream stream) {
+  w4_route_mask = 0;
   MI355X_REQUIRE(sk_out != nullptr, MI355X_EINVAL, "awq_gemm_deferred: sk_out is null");
   *sk_out = 0;
   GemmArgs g{c, a, qweight, scales, qzeros, workspace, workspace_elems, dq_workspace,
@@ -703,6 +728,7 @@ int mi355x_awq_gemm_silu_mul(void* out, const void* a, const uint32_t* qweight, 
                              const uint32_t* qzeros, void* dq_workspace, int64_t dq_workspace_bytes,
                              int m, int n, int k, int group_size, int64_t lda, int dtype,
                              mi355x_stream stream) {
+  w4_route_mask = 0;
   GemmArgs g{out, a, qweight, scales, qzeros, nullptr, 0, dq_workspace, dq_workspace_bytes,
              m, n, k, group_size, lda, kZeroAwq, static_cast<hipStream_t>(stream)};
   g.fuse_silu = true;
@@ -721,6 +747,7 @@ int mi355x_awq_gemm_silu_mul_packed(void* out_packed, const void* a, const uint3
                                     const void* scales, const uint32_t* qzeros, void* dq_workspace,
                                     int64_t dq_workspace_bytes, int m, int n, int k, int group_size,
                                     int64_t lda, int dtype, mi355x_stream stream) {
+  w4_route_mask = 0;
   GemmArgs g{out_packed, a, qweight, scales, qzeros, nullptr, 0, dq_workspace, dq_workspace_bytes,
              m, n, k, group_size, lda, kZeroAwq, static_cast<hipStream_t>(stream)};
   g.fuse_silu = true;
@@ -741,6 +768,7 @@ int mi355x_awq_gemm_packed_a(void* out, const void* a_packed, const uint32_t* qw
                              const void* scales, const uint32_t* qzeros, void* dq_workspace,
                              int64_t dq_workspace_bytes, int m, int n, int k, int group_size,
                              int dtype, mi355x_stream stream) {
+  w4_route_mask = 0;
   GemmArgs g{out, a_packed, qweight, scales, qzeros, nullptr, 0, dq_workspace, dq_workspace_bytes,
              m, n, k, group_size, k, kZeroAwq, static_cast<hipStream_t>(stream)};
   g.a_packed = true;
@@ -774,6 +802,7 @@ int mi355x_w4a16_prepack(void* image, const uint32_t* qweight, const void* scale
 int mi355x_w4a16_gemm_prepacked(void* out, const void* a, const void* image, void* a_workspace,
                                 int64_t a_workspace_bytes, int m, int n, int k, int64_t lda, int mode,
                                 int dtype, mi355x_stream stream) {
+  w4_route_mask = 0;
   MI355X_REQUIRE(m >= 0 && n > 0 && k > 0 && n % 64 == 0 && k % 32 == 0, MI355X_EUNSUPPORTED,
                  "w4a16_gemm_prepacked: bad sizes m=%d n=%d k=%d", m, n, k);
   if (m == 0) return MI355X_OK;
@@ -812,6 +841,7 @@ int mi355x_gptq_gemm(void* c, const void* a, const uint32_t* qweight,
                      void* perm_space, float* workspace, int64_t workspace_elems,
                      void* dq_workspace, int64_t dq_workspace_bytes, int m, int n, int k, int bit,
                      int group_size, int dtype, mi355x_stream stream) {
+  w4_route_mask = 0;
   MI355X_REQUIRE(bit == 4 || bit == 8, MI355X_EUNSUPPORTED,
                  "gptq_gemm: 4-bit and 8-bit weights are implemented (bit=%d)", bit);
   GemmArgs g{c, a, qweight, scales, qzeros, workspace, workspace_elems, dq_workspace,
@@ -833,5 +863,7 @@ int mi355x_gptq_gemm(void* c, const void* a, const uint32_t* qweight,
   }
   return MI355X_DISPATCH_HALF(dtype, [&] { return run_gemm_t<scalar_t>(g, dtype); });
 }
+
+int mi355x_w4a16_last_route(void) { return w4_route_mask; }
 
 }  // extern "C"

@@ -185,6 +185,7 @@ static int launch_large(const GemmArgs& g) {
                        static_cast<const T*>(g.scales), g.qz, g.m, g.n, g.k, g.group, g.lda,
                        num_m_blocks, num_tiles);
   }
+  w4_route_note(MI355X_W4_ROUTE_LARGE_M);
   return check_launch("w4a16_gemm_large_m");
 }
 

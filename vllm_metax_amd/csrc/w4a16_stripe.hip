@@ -572,6 +572,7 @@ static int launch_stripe_cfg(const GemmArgs& g, const T* a, T* c, int rows, cons
   hipLaunchKernelGGL(kern, dim3(stripes, p.sk), dim3(Cfg::THREADS), Cfg::LDS_BYTES, g.stream, c, g.ws,
                      a, g.lda, g.qw, static_cast<const T*>(g.scales), g.qz,
                      rows, g.n, g.k, g.group, p.steps);
+  w4_route_note(MI355X_W4_ROUTE_STRIPE);
   return check_launch("w4a16_gemm_stripe");
 }
 
@@ -638,6 +639,7 @@ static int run_stripe(const GemmArgs& g, int row0, int rows) {
     const int64_t n4 = (int64_t)rows * g.n / 4;
     hipLaunchKernelGGL(w4a16_sum_slabs_kernel<T>, dim3((n4 + 255) / 256), dim3(256), 0, g.stream, c,
                        g.ws, n4, p.sk);
+    w4_route_note(MI355X_W4_ROUTE_SUM_SLABS);
     rc = check_launch("w4a16_sum_slabs");
   }
   return rc;

@@ -468,6 +468,7 @@ static int run_unfused(const GemmArgs& g) {
                        g.stream, packed_a_dst, static_cast<const T*>(g.a), g.m, g.k, g.lda);
     rc = check_launch("pack_a");
     if (rc) return rc;
+    w4_route_note(MI355X_W4_ROUTE_PACK_A);
   }
   const int num_m_blocks = (g.m + kUfBM - 1) / kUfBM;
   // SILU: a tile = 128 gate + 128 up columns, i.e. one block per 128 output columns
@@ -503,7 +504,9 @@ static int run_unfused(const GemmArgs& g) {
                      reinterpret_cast<const uint4*>(packed_a), reinterpret_cast<const uint4*>(packed_b),
                      g.m, g.n, g.k, num_m_blocks, num_tiles, slabs, sk);
   rc = check_launch("gemm_packed");
+  w4_route_note(MI355X_W4_ROUTE_IMAGE);
   if (rc || sk == 1) return rc;
+  w4_route_note(MI355X_W4_ROUTE_SUM_SLABS);
   if constexpr (SILU) {
     const int64_t rows = MODE == 2 ? ((int64_t)g.m + 15) / 16 * 16 : g.m;
     const int64_t threads = rows * (g.n / 16);
