@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MI355X_ABI_VERSION 6   /* 6: + w4a16_last_route and the MI355X_W4_ROUTE_* bits (additive, host-side diagnostic); 5: + paged_attention_v2_ps, scaled_mm_fp8_deferred and its slab consumers, scaled_mm_prepack(ed), scaled_mm_split_elems, w4a16_prepacked_split_elems (additive; w4a16_gemm_prepacked takes m >= 384); 4: + paged_prefill_attention_alibi, silu_and_mul_per_token_quant (additive); 3: + greedy_advance, paged_attention_fused_qkv, *_rms_norm_image, paged_prefill_attention_image (additive);
+#define MI355X_ABI_VERSION 6   /* 6: + w4a16_last_route and the MI355X_W4_ROUTE_* bits (additive, host-side diagnostic), + paged_prefill_last_route and MI355X_PF_ROUTE_* (additive as well: the version stays 6); 5: + paged_attention_v2_ps, scaled_mm_fp8_deferred and its slab consumers, scaled_mm_prepack(ed), scaled_mm_split_elems, w4a16_prepacked_split_elems (additive; w4a16_gemm_prepacked takes m >= 384); 4: + paged_prefill_attention_alibi, silu_and_mul_per_token_quant (additive); 3: + greedy_advance, paged_attention_fused_qkv, *_rms_norm_image, paged_prefill_attention_image (additive);
                                 * 2 was BREAKING (kv_cache_dtype / k_scale / v_scale inserted before `stream` in reshape_and_cache*,
                                 * paged_attention_v1/_v2, paged_prefill_attention): a binding must refuse a library whose
                                 * mi355x_abi_version() differs from the version it was written for (vllm_metax_amd/_abi.py does) */
@@ -184,7 +184,8 @@ int mi355x_paged_attention_v2_ps(void* out, float* exp_sums, float* max_logits,
  * cu_seqlens_q int32 [num_seqs+1]; seq_lens int32 [num_seqs] = context + new.
  * sliding_window W > 0: a query sees only its last W keys (the call site's window_size = (W-1, 0));
  * softcap c > 0: scores become c * tanh(s / c) before the mask; 0 = off.  For head_size 128 / block_size 16 /
- * 16-bit types both run on the MFMA kernel (a separate instantiation), other shapes on the general kernel.
+ * 16-bit types both run on the MFMA kernel (a separate instantiation), for head_size 64 and 256 on the MFMA kernel
+ * of those head sizes (prefill_attention_hd.hip), other shapes on the general kernel.
  * ref (call site, third-party kernel): vllm_metax/v1/attention/backends/
  *      flash_attn.py:725-747; semantic oracle tests/kernels/attention/
  *      test_flash_attn.py:27-80. */
@@ -213,6 +214,17 @@ int mi355x_paged_prefill_attention_alibi(void* out, const void* query, const voi
                                          int dtype, int kv_cache_dtype, const float* k_scale,
                                          const float* v_scale, int sliding_window, float softcap,
                                          const float* alibi_slopes, mi355x_stream stream);
+
+/* Host-side diagnostic: the kernel the most recent prefill entry (mi355x_paged_prefill_attention, .._alibi,
+ * .._image) launched on the calling thread; 0 when it launched nothing (an error, an empty batch, the image form
+ * answering "not applicable").  Every entry clears it first.  The tests assert the route of every shape with it:
+ * the general kernel serves every shape, so a tolerance test alone cannot tell which kernel ran. */
+enum {
+  MI355X_PF_ROUTE_GENERIC = 1,  /* paged_prefill_generic_kernel (prefill_attention.hip)                          */
+  MI355X_PF_ROUTE_D128 = 2,     /* paged_prefill_d128_kernel: head_size 128, block_size 16, 16-bit types         */
+  MI355X_PF_ROUTE_HD = 3        /* paged_prefill_hd_kernel: head_size 64 / 256 (prefill_attention_hd.hip)        */
+};
+int mi355x_paged_prefill_last_route(void);
 
 /* ------------------------------------------------------------- layernorm --
  * ref: csrc/layernorm_kernels.cu:141-162 (rms_norm), :174-217 (fused_add). */

@@ -313,6 +313,17 @@ def paged_prefill_attention(out: torch.Tensor, query: torch.Tensor, key_cache: t
     _abi.check(rc, "paged_prefill_attention")
 
 
+# MI355X_PF_ROUTE_* (include/mi355x_hotpath.h): the values of paged_prefill_last_route()
+PF_ROUTE_GENERIC, PF_ROUTE_D128, PF_ROUTE_HD = 1, 2, 3
+
+
+def paged_prefill_last_route() -> int:
+    """The kernel the most recent prefill attention call of this thread launched (general kernel, the MFMA kernel of
+    head size 128, the MFMA kernel of head sizes 64 / 256); 0 when it launched nothing.  A host-side diagnostic for
+    the tests, which assert every shape's route."""
+    return int(_abi.load().mi355x_paged_prefill_last_route())
+
+
 # ------------------------------------------------------------------------- layernorm
 def rms_norm(out: torch.Tensor, input: torch.Tensor, weight: torch.Tensor,
              epsilon: float) -> None:

@@ -8,7 +8,14 @@
 // tests/kernels/attention/test_flash_attn.py:27-80 (fp32 scores and softmax, probabilities
 // rounded to the value dtype, fp32 PV accumulation).
 //
-// MI355X design (fast path: head_size 128, block_size 16, 16-bit types):
+// Three kernels, chosen by paged_prefill_impl (mi355x_paged_prefill_last_route tells which one ran):
+//   * paged_prefill_d128_kernel (below): head_size 128, block_size 16, 16-bit types — plain, window / soft-cap /
+//     ALiBi, operand-image output, in-kernel rotary;
+//   * paged_prefill_hd_kernel (prefill_attention_hd.hip): head_size 64 and 256, block_size 16, 16-bit types —
+//     plain and window / soft-cap, the same formulation on a schedule of its own per head size;
+//   * paged_prefill_generic_kernel (below): everything else.
+//
+// MI355X design (head_size 128, block_size 16, 16-bit types):
 //   * one 256-thread workgroup = 128 consecutive query tokens of one (sequence, q-head);
 //     each wave owns 32 query rows (2 MFMA column tiles);
 //   * the x-split layout is MFMA-shaped by construction: a 16-token K block
@@ -26,85 +33,15 @@
 //     verbatim as well; a lane's MFMA fragment is 8 bytes of K (ds_read_b64) or 4 + 4 bytes of V,
 //     converted exactly to scalar_t in registers (v_cvt_scalef32_pk_*_fp8, scale 1); k_scale is
 //     folded into the softmax scale and v_scale into the final 1/l.
-#include "common.cuh"
+#include "prefill_attention.cuh"
 
 namespace mi355x {
-
-template <typename T>
-struct MfmaQK;
-template <>
-struct MfmaQK<bf16_t> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& a, const uint4& b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                   __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-    bf16x2_t v = {static_cast<bf16_t>(lo), static_cast<bf16_t>(hi)};
-    return __builtin_bit_cast(uint32_t, v);
-  }
-  // 4 e4m3 (E5M2: e5m2) bytes -> 4 bf16 (two packed words), exact
-  template <bool E5M2 = false>
-  static __device__ __forceinline__ uint2 from_fp8x4(uint32_t w) {
-    if constexpr (E5M2)
-      return make_uint2(
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w, 1.0f, false)),
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w, 1.0f, true)));
-    else
-      return make_uint2(
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false)),
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true)));
-  }
-};
-template <>
-struct MfmaQK<f16_t> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& a, const uint4& b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a),
-                                                  __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-    f16x2_t v = {static_cast<f16_t>(lo), static_cast<f16_t>(hi)};
-    return __builtin_bit_cast(uint32_t, v);
-  }
-  template <bool E5M2 = false>
-  static __device__ __forceinline__ uint2 from_fp8x4(uint32_t w) {
-    if constexpr (E5M2)
-      return make_uint2(
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w, 1.0f, false)),
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w, 1.0f, true)));
-    else
-      return make_uint2(
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false)),
-          __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true)));
-  }
-};
-
-// all-reduce over the four 16-lane rows of a wave (lanes l, l ^ 16, l ^ 32, l ^ 48) in registers: gfx950's
-// v_permlane16_swap / v_permlane32_swap exchange row pairs / wave halves (vdst's odd rows with src's even rows;
-// vdst's upper half with src's lower half), so op(swap(x, x)) is the xor-16 / xor-32 butterfly step without the
-// LDS round trip of ds_bpermute (__shfl_xor).
-__device__ __forceinline__ float rows_max(float x) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, x);
-  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  x = fmaxf(__builtin_bit_cast(float, (uint32_t)r[0]), __builtin_bit_cast(float, (uint32_t)r[1]));
-  const uint32_t v = __builtin_bit_cast(uint32_t, x);
-  auto q = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return fmaxf(__builtin_bit_cast(float, (uint32_t)q[0]), __builtin_bit_cast(float, (uint32_t)q[1]));
-}
-__device__ __forceinline__ float rows_sum(float x) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, x);
-  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  x = __builtin_bit_cast(float, (uint32_t)r[0]) + __builtin_bit_cast(float, (uint32_t)r[1]);
-  const uint32_t v = __builtin_bit_cast(uint32_t, x);
-  auto q = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return __builtin_bit_cast(float, (uint32_t)q[0]) + __builtin_bit_cast(float, (uint32_t)q[1]);
-}
 
 constexpr int kPfD = 128;
 constexpr int kPfBS = 16;
 constexpr int kPfQTile = 128;   // query rows per workgroup
 constexpr int kPfKvTile = 32;   // keys per stage (2 cache blocks)
 constexpr int kPfStages = 3;    // LDS ring depth (16 KiB per stage)
-constexpr float kNegBig = -1.0e30f;
 
 // IMG: `out` is the activation operand image of the prefill GEMM that consumes the attention output (o_proj):
 // [row tile of 16 tokens][k tile of 32][64 slots of 8 elements], slot lr * 16 + (lc ^ g(lr)) = O[16 mt + lc][32 kt +
@@ -487,7 +424,9 @@ __global__ __launch_bounds__(256, 2) void paged_prefill_d128_kernel(
 
 // ---------------------------------------------------------------------------------------
 // Generic fallback (any head size / block size / dtype): one wave per (query token, head),
-// lanes stride over keys, two passes (max+sum, then PV).  Correctness path only.
+// lanes stride over keys, two passes (max+sum, then PV).  Correctness path only.  What still lands here: fp32;
+// block_size != 16; head sizes other than 64 / 128 / 256 (80, 96, 112, 120, 192, ...); operands that miss the
+// alignment of the MFMA kernels (q rows 16-byte, out 8-byte, cache strides 16-byte).
 template <typename CT>
 __device__ __forceinline__ float cache_to_f32(CT v) {
   if constexpr (std::is_same<CT, e5m2_t>::value) return bf8_to_f32(v.v);
@@ -571,6 +510,8 @@ __global__ __launch_bounds__(64) void paged_prefill_generic_kernel(
 
 using namespace mi355x;
 
+thread_local int mi355x::pf_route = 0;
+
 static int paged_prefill_impl(
     void* out, const void* query, const void* key_cache, const void* value_cache, int num_seqs,
     int num_heads, int num_kv_heads, int head_size, int block_size, float scale,
@@ -580,6 +521,7 @@ static int paged_prefill_impl(
     const float* v_scale, int sliding_window, float softcap, mi355x_stream stream, bool image,
     const int64_t* positions = nullptr, const void* cos_sin_cache = nullptr,
     const float* alibi_slopes = nullptr) {
+  pf_route = 0;
   MI355X_REQUIRE(sliding_window >= 0 && softcap >= 0.f, MI355X_EINVAL,
                  "paged_prefill_attention: sliding_window / softcap must be >= 0 (0 = off)");
   MI355X_REQUIRE(kv_cache_dtype == MI355X_KV_AUTO || kv_cache_dtype == MI355X_KV_FP8_E4M3 ||
@@ -603,16 +545,27 @@ static int paged_prefill_impl(
   hipStream_t s = static_cast<hipStream_t>(stream);
   // sliding window / soft-cap / ALiBi run on the OPTS instantiation of the MFMA kernel
   const bool opts = sliding_window > 0 || softcap > 0.f || alibi_slopes != nullptr;
-  const bool fast = head_size == 128 && block_size == 16 && dtype != MI355X_F32 &&
+  const bool aligned = block_size == 16 && dtype != MI355X_F32 &&
                     q_stride % 8 == 0 && out_stride % 4 == 0 &&
                     ((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(key_cache) |
                       reinterpret_cast<uintptr_t>(value_cache)) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 7) == 0 &&
                     kv_block_stride % (kv8 ? 16 : 8) == 0 && kv_head_stride % (kv8 ? 16 : 8) == 0;
+  const bool fast = aligned && head_size == 128;
   if (image && !(fast && !opts && (reinterpret_cast<uintptr_t>(out) & 15) == 0)) return 1;   // image form: plain fast path only
   MI355X_REQUIRE(fast || alibi_slopes == nullptr, MI355X_EUNSUPPORTED,
                  "paged_prefill_attention: alibi_slopes need head_size 128, block_size 16 and a 16-bit dtype");
+  if (aligned && !image && (head_size == 64 || head_size == 256)) {
+    // the MFMA kernel of the other two head sizes (prefill_attention_hd.hip); ALiBi was refused above
+    const PrefillArgs a = {out, query, key_cache, value_cache, num_seqs, num_heads, num_kv_heads, head_size, scale,
+                           block_tables, seq_lens, cu_seqlens_q, max_query_len, max_num_blocks_per_seq, q_stride,
+                           out_stride, kv_block_stride, kv_head_stride, dtype, kv_cache_dtype, k_scale, v_scale,
+                           sliding_window, softcap, s};
+    pf_route = MI355X_PF_ROUTE_HD;
+    return paged_prefill_hd_launch(a);
+  }
   if (fast) {
+    pf_route = MI355X_PF_ROUTE_D128;
     // 128 query rows per workgroup — 64 when that leaves fewer than two workgroups per CU (chunked prefill of one or
     // two sequences, a TP shard's few heads: a workgroup is a serial chain over its key stages, and 128 workgroups take
     // as long as 512; MI355X_PF_QT=1|2 forces a shape for A/B runs)
@@ -659,6 +612,7 @@ static int paged_prefill_impl(
   const int64_t max_tokens = (int64_t)num_seqs * max_query_len;
   MI355X_REQUIRE(max_tokens <= 0x7fffffff, MI355X_EUNSUPPORTED, "paged_prefill_attention: too many tokens");
   dim3 grid((int)max_tokens, num_heads), block(64);
+  pf_route = MI355X_PF_ROUTE_GENERIC;
   return MI355X_DISPATCH_FLOAT(dtype, [&] {
     if (kv8 && e5m2) {
       hipLaunchKernelGGL((paged_prefill_generic_kernel<scalar_t, e5m2_t>), grid, block,
@@ -716,6 +670,8 @@ extern "C" int mi355x_paged_prefill_attention_alibi(
                             kv_cache_dtype, k_scale, v_scale, sliding_window, softcap, stream, false, nullptr,
                             nullptr, alibi_slopes);
 }
+
+extern "C" int mi355x_paged_prefill_last_route(void) { return pf_route; }
 
 // returns 1 (no error) when the image form does not apply: run mi355x_paged_prefill_attention instead
 extern "C" int mi355x_paged_prefill_attention_image(
