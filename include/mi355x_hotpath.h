@@ -437,9 +437,13 @@ enum {
   MI355X_W4_ROUTE_LARGE_M = 4,     /* w4a16_gemm_large_m_kernel, the 128 x 256 tile kernel (w4a16_large.hip)   */
   MI355X_W4_ROUTE_IMAGE = 8,       /* gemm_packed_kernel on operand images, per call or prepacked (w4a16_unfused.hip) */
   MI355X_W4_ROUTE_ANY_N4 = 16,     /* w4a16_gemm_any_n_kernel (n % 64 != 0)                                    */
-  MI355X_W4_ROUTE_ANY_8 = 32,      /* w8a16_gemm_any_kernel (8-bit GPTQ below 1024 rows)                       */
+  MI355X_W4_ROUTE_ANY_8 = 32,      /* w8a16_gemm_any_kernel (8-bit GPTQ shapes the stream kernel does not take) */
   MI355X_W4_ROUTE_PACK_A = 64,     /* pack_a_kernel: activations re-tiled into operand images first            */
   MI355X_W4_ROUTE_SUM_SLABS = 128  /* K was split: fp32 slabs added by w4a16_sum_slabs(_silu)_kernel           */
+};
+/* one more bit of the same mask, for the 8-bit GPTQ kernels */
+enum {
+  MI355X_W8_ROUTE_STREAM = 256     /* w8a16_gemm_stream_kernel (w8a16_stream.hip): 8-bit GPTQ, n % 64 == 0, k % 128 == 0 */
 };
 int mi355x_w4a16_last_route(void);
 

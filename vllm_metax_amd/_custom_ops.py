@@ -636,11 +636,13 @@ def silu_and_mul_quant(out: torch.Tensor, input: torch.Tensor, scale: torch.Tens
 _DQ_SCRATCH: dict = {}
 
 
-def _dq_scratch(m: int, n: int, k: int, device) -> Optional[torch.Tensor]:
+def _dq_scratch(m: int, n: int, k: int, device, bits: int = 4) -> Optional[torch.Tensor]:
     """Scratch for the dequantised weights of a prefill-sized GEMM (one buffer per device,
     grown to the largest n*k seen; the kernels of one stream run in order, so sharing is safe)."""
     m_pad = (m + 15) // 16 * 16
-    if m <= 64:
+    if bits == 8 and m < 1024:
+        need = 8 * 64 * n * 4                   # 8-bit stream kernel: fp32 split-K slabs of one 64-row pass
+    elif m <= 64:
         # decode: packed activations only, as many 16-row tiles as the kernel variant reads (1, 2 or 4)
         need = (16 if m <= 16 else 32 if m <= 32 else 64) * k * 2
     elif m < 1024:
@@ -654,6 +656,7 @@ def _dq_scratch(m: int, n: int, k: int, device) -> Optional[torch.Tensor]:
 # MI355X_W4_ROUTE_* (include/mi355x_hotpath.h): the bits of w4a16_last_route()
 W4_ROUTE_STRIPE, W4_ROUTE_SMALL_M, W4_ROUTE_LARGE_M, W4_ROUTE_IMAGE = 1, 2, 4, 8
 W4_ROUTE_ANY_N4, W4_ROUTE_ANY_8, W4_ROUTE_PACK_A, W4_ROUTE_SUM_SLABS = 16, 32, 64, 128
+W8_ROUTE_STREAM = 256   # MI355X_W8_ROUTE_STREAM: w8a16_gemm_stream_kernel, a bit of the same mask
 
 
 def w4a16_last_route() -> int:
@@ -1182,7 +1185,7 @@ def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor, b_gptq_qzeros: torch.Te
     ws = temp_space if (temp_space is not None and temp_space.is_cuda
                         and temp_space.dtype == torch.float32 and temp_space.numel() > 0) else None
     out = torch.empty((m, n), dtype=a.dtype, device=a.device)
-    dq = _dq_scratch(m, n, k, a.device)
+    dq = _dq_scratch(m, n, k, a.device, bit)
     rc = _abi.load().mi355x_gptq_gemm(_ptr(out), _ptr(a), _ptr(b_q_weight), _ptr(b_gptq_qzeros),
                                       _ptr(b_gptq_scales), _ptr(g_idx), _ptr(pspace), _ptr(ws),
                                       ws.numel() if ws is not None else 0, _ptr(dq),

@@ -398,6 +398,7 @@ Tensor gptq_gemm(Tensor a, Tensor b_q_weight, Tensor b_gptq_qzeros, Tensor b_gpt
   if (m >= 1024)   // operand images + the partial tiles of a K split (shapes with few 256 x 256 tiles)
     dq = at::empty({(n + (m + 15) / 16 * 16) * k * 2 + 4 * mi355x_w4a16_prepacked_split_elems((int)m, (int)n, (int)k)},
                    a.options().dtype(at::kByte));
+  else if (bit == 8) dq = at::empty({8 * 64 * n * 4}, a.options().dtype(at::kByte));   // split-K slabs of a 64-row pass (8-bit stream kernel)
   else if (m > 64) dq = at::empty({8 * 128 * n * 4}, a.options().dtype(at::kByte));   // split-K slabs of a 128-row pass
   ok(mi355x_gptq_gemm(out.data_ptr(), a.data_ptr(),
                       static_cast<const uint32_t*>(b_q_weight.data_ptr()),

@@ -335,6 +335,7 @@ int w4a16_gemm_unfused_dispatch(const GemmArgs& g, int dtype);  // w4a16_unfused
 int w4a16_prepack_dispatch(const GemmArgs& g, int dtype);       // w4a16_unfused.hip
 int w4a16_gemm_stripe_dispatch(const GemmArgs& g, int dtype, int row0, int rows);  // w4a16_stripe.hip
 int w4a16_gemm_stripe_silu_dispatch(const GemmArgs& g, int dtype);                  // w4a16_stripe.hip
+int w8a16_gemm_stream_dispatch(const GemmArgs& g, int dtype, int row0, int rows);   // w8a16_stream.hip
 
 template <typename T, int ZMODE>
 static int launch_small_m(const GemmArgs& g, int row0, int rows) {
@@ -466,8 +467,8 @@ __global__ __launch_bounds__(256) void w4a16_gemm_any_n_kernel(
 }
 
 // 8-bit GPTQ, any shape: same structure (16 columns x 8 rows per workgroup, 16 k-parts), 4 k per word.
-// Decode-sized 8-bit GEMMs run here: a correctness path (the int4 stripe kernel has no 8-bit twin;
-// m >= 1024 goes through the operand-image GEMM).
+// A correctness path for the 8-bit shapes w8a16_gemm_stream_kernel (w8a16_stream.hip) does not take
+// (n % 64 != 0, k % 128 != 0); m >= 1024 goes through the operand-image GEMM.
 template <typename T>
 __global__ __launch_bounds__(256) void w8a16_gemm_any_kernel(
     T* __restrict__ c, const T* __restrict__ a, const uint32_t* __restrict__ qw,
@@ -548,7 +549,21 @@ static int run_gemm_t(const GemmArgs& g, int dtype) {
       int rc = w4a16_gemm_unfused_dispatch(g, dtype);
       if (rc != 1) return rc;
     }
-    return launch_any_n<T>(g);
+    // below 1024 rows (or no scratch for the operand images): passes of up to 64 rows through the stream kernel,
+    // split-K slabs in the fp32 workspace or, when the caller gave none, in the scratch
+    GemmArgs gm = g;
+    if ((gm.ws == nullptr || (reinterpret_cast<uintptr_t>(gm.ws) & 15) != 0) && g.dq_ws != nullptr &&
+        (reinterpret_cast<uintptr_t>(g.dq_ws) & 15) == 0) {
+      gm.ws = static_cast<float*>(g.dq_ws);
+      gm.ws_elems = g.dq_ws_bytes / 4;
+    }
+    for (int row0 = 0; row0 < g.m; row0 += 64) {
+      const int rows = (g.m - row0) < 64 ? (g.m - row0) : 64;
+      const int rc = w8a16_gemm_stream_dispatch(gm, dtype, row0, rows);
+      if (rc == 1 && row0 == 0) return launch_any_n<T>(g);   // (a refusal depends on the shape, not on the pass)
+      if (rc) return rc;
+    }
+    return MI355X_OK;
   }
   if (g.m >= 1024) {
     int rc = w4a16_gemm_unfused_dispatch(g, dtype);
