@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MI355X_ABI_VERSION 6   /* 6: + w4a16_last_route and the MI355X_W4_ROUTE_* bits (additive, host-side diagnostic), + paged_prefill_last_route and MI355X_PF_ROUTE_* (additive as well: the version stays 6); 5: + paged_attention_v2_ps, scaled_mm_fp8_deferred and its slab consumers, scaled_mm_prepack(ed), scaled_mm_split_elems, w4a16_prepacked_split_elems (additive; w4a16_gemm_prepacked takes m >= 384); 4: + paged_prefill_attention_alibi, silu_and_mul_per_token_quant (additive); 3: + greedy_advance, paged_attention_fused_qkv, *_rms_norm_image, paged_prefill_attention_image (additive);
+#define MI355X_ABI_VERSION 6   /* 6: + scaled_mm_fp8_block, per_token_group_fp8_quant, scaled_mm_block_last_route and MI355X_F8B_ROUTE_* (additive: the version stays 6), + w4a16_last_route and the MI355X_W4_ROUTE_* bits (additive, host-side diagnostic), + paged_prefill_last_route and MI355X_PF_ROUTE_* (additive as well: the version stays 6); 5: + paged_attention_v2_ps, scaled_mm_fp8_deferred and its slab consumers, scaled_mm_prepack(ed), scaled_mm_split_elems, w4a16_prepacked_split_elems (additive; w4a16_gemm_prepacked takes m >= 384); 4: + paged_prefill_attention_alibi, silu_and_mul_per_token_quant (additive); 3: + greedy_advance, paged_attention_fused_qkv, *_rms_norm_image, paged_prefill_attention_image (additive);
                                 * 2 was BREAKING (kv_cache_dtype / k_scale / v_scale inserted before `stream` in reshape_and_cache*,
                                 * paged_attention_v1/_v2, paged_prefill_attention): a binding must refuse a library whose
                                 * mi355x_abi_version() differs from the version it was written for (vllm_metax_amd/_abi.py does) */
@@ -283,6 +283,15 @@ int mi355x_dynamic_per_token_scaled_fp8_quant(void* out, const void* input,
                                               int64_t in_row_stride,
                                               int64_t out_row_stride, int dtype,
                                               mi355x_stream stream);
+/* Per token and 128-wide group (the activation side of mi355x_scaled_mm_fp8_block): scale = max(absmax of the group,
+ * eps) / 448, q = sat_e4m3(float(x) / scale), the exact division.  scales[token * scale_row_stride + group *
+ * scale_group_stride]: (hidden_size / 128, 1) is the row-major [num_tokens, groups] layout, (1, num_tokens) the
+ * token-contiguous "column-major scales".  f16 / bf16 input, hidden_size % 128 == 0, row strides multiples of 8
+ * elements; any group_size but 128 returns MI355X_EUNSUPPORTED. */
+int mi355x_per_token_group_fp8_quant(void* out, float* scales, const void* input, int num_tokens,
+                                     int hidden_size, int group_size, int64_t in_row_stride,
+                                     int64_t out_row_stride, int64_t scale_row_stride,
+                                     int64_t scale_group_stride, float eps, int dtype, mi355x_stream stream);
 
 /* ------------------------------------------------------------------ rotary --
  * In-place RoPE on query and (optional) key. positions int64 [num_tokens].
@@ -604,6 +613,32 @@ int mi355x_scaled_mm_fp8(void* out, const void* a, const void* b, const float* a
                          const void* bias, float* workspace, int64_t workspace_elems, int m,
                          int n, int k, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
                          mi355x_stream stream);
+
+/* Block-scaled fp8 GEMM (csrc/fp8_block_gemm.hip): weights with one fp32 scale per 128 x 128 block, activations with
+ * one per token and 128-wide K group (mi355x_per_token_group_fp8_quant) — the capability the reference names
+ * cutlass_scaled_mm_supports_block_fp8 (csrc/torch_bindings.cpp:273-278) and answers false.  KB = k / 128,
+ * NB = ceil(n / 128):
+ *   out[i, j] = T( sum_kb a_s[i, kb] * b_s[kb, j / 128] * (sum_{kk in block kb} a[i, kk] * b[kk, j]) + bias[j] )
+ * a [m, k] row-major e4m3fn, b [k, n] column-major e4m3fn (ldb = b.stride(1)); a_scales[i * a_s_row_stride + kb *
+ * a_s_kb_stride], b_scales[kb * b_s_kb_stride + nb * b_s_nb_stride] (a checkpoint's [NB, KB] tensor is its own .t():
+ * strides (1, KB)).  Requires k % 128 == 0, n % 16 == 0 (the last column block may be ragged), a, b, out 16-byte
+ * aligned, lda, ldb, ldc * sizeof(T) multiples of 16 bytes; anything else returns MI355X_EUNSUPPORTED.
+ * `workspace` (fp32 elements, 16-byte aligned, may be NULL): sk * min(m, 64) * n elements let the m <= 320 kernel
+ * split K sk <= 16 ways, mi355x_scaled_mm_split_elems(m, n, k) elements the m > 320 kernel; the slabs hold scaled
+ * partial sums, added in slab order by a finish launch (no memset, no atomics: HIP-graph-replayable). */
+int mi355x_scaled_mm_fp8_block(void* out, const void* a, const void* b, const float* a_scales,
+                               int64_t a_s_row_stride, int64_t a_s_kb_stride, const float* b_scales,
+                               int64_t b_s_kb_stride, int64_t b_s_nb_stride, const void* bias, float* workspace,
+                               int64_t workspace_elems, int m, int n, int k, int64_t lda, int64_t ldb, int64_t ldc,
+                               int out_dtype, mi355x_stream stream);
+/* Host-side diagnostic, as mi355x_w4a16_last_route: the kernels the most recent mi355x_scaled_mm_fp8_block on the
+ * calling thread launched; the entry clears the mask first. */
+enum {
+  MI355X_F8B_ROUTE_DECODE = 1,     /* f8b_decode_kernel: m <= 320, passes of 64 rows                            */
+  MI355X_F8B_ROUTE_TILE = 2,       /* f8b_tile_kernel: the 256 x 256 tile kernel                                */
+  MI355X_F8B_ROUTE_SUM_SLABS = 4   /* K was split: scaled fp32 slabs added by f8b_finish_kernel                 */
+};
+int mi355x_scaled_mm_block_last_route(void);
 
 /* Shapes with few 256 x 256 output tiles (chunked-prefill sized m, the narrow n of a TP shard) split K inside the
  * m > 320 kernel when the workspace has room for the partial tiles: mi355x_scaled_mm_split_elems returns the 4-byte

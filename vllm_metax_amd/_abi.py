@@ -63,6 +63,7 @@ PROTOTYPES = {
     "mi355x_static_scaled_fp8_quant": (_I, [_P, _P, _P, _I, _I, _L, _L, _I, _P]),
     "mi355x_dynamic_scaled_fp8_quant": (_I, [_P, _P, _P, _I, _I, _L, _L, _I, _P]),
     "mi355x_dynamic_per_token_scaled_fp8_quant": (_I, [_P, _P, _P, _P, _I, _I, _L, _L, _I, _P]),
+    "mi355x_per_token_group_fp8_quant": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P]),
     "mi355x_rotary_embedding": (
         _I, [_P, _P, _P, _P, _I, _I, _L, _L, _L, _I, _I, _I, _I, _I, _P]),
     "mi355x_batched_rotary_embedding": (
@@ -105,6 +106,9 @@ PROTOTYPES = {
     "mi355x_dynamic_scaled_int8_quant": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
     "mi355x_scaled_mm_fp8": (
         _I, [_P, _P, _P, _P, _I, _P, _I, _P, _P, _L, _I, _I, _I, _L, _L, _L, _I, _P]),
+    "mi355x_scaled_mm_fp8_block": (
+        _I, [_P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _P, _L, _I, _I, _I, _L, _L, _L, _I, _P]),
+    "mi355x_scaled_mm_block_last_route": (_I, []),
     "mi355x_scaled_mm_prepack": (_I, [_P, _P, _I, _I, _L, _P]),
     "mi355x_scaled_mm_split_elems": (_L, [_I, _I, _I]),
     "mi355x_scaled_mm_prepacked": (

@@ -1323,6 +1323,65 @@ def cutlass_scaled_mm_supports_fp8(cuda_device_capability: int) -> bool:
     return True
 
 
+def cutlass_scaled_mm_supports_block_fp8(cuda_device_capability: int) -> bool:
+    """The reference returns False (torch_bindings.cpp:273-278); here: the block form of cutlass_scaled_mm."""
+    return True
+
+
+# MI355X_F8B_ROUTE_* (include/mi355x_hotpath.h): the bits of scaled_mm_block_last_route()
+F8B_ROUTE_DECODE, F8B_ROUTE_TILE, F8B_ROUTE_SUM_SLABS = 1, 2, 4
+
+
+def scaled_mm_block_last_route() -> int:
+    """Mask of the kernels the most recent block-scaled cutlass_scaled_mm on this thread launched."""
+    return int(_abi.load().mi355x_scaled_mm_block_last_route())
+
+
+def _scaled_mm_fp8_block(out, a, b, a_scales, b_scales, bias) -> None:
+    """cutlass_scaled_mm with a_scales [m, k / 128] and b_scales [k / 128, ceil(n / 128)] (fp8_block_gemm.hip); the
+    scales go through with their strides, so a checkpoint's [n / 128, k / 128] tensor is passed as its .t()."""
+    m, k = a.shape
+    n = b.size(1)
+    if a_scales.dtype != torch.float32 or b_scales.dtype != torch.float32:
+        raise RuntimeError("cutlass_scaled_mm: scales must be float32")
+    if bias is not None and (bias.numel() != n or not bias.is_contiguous() or bias.dtype != out.dtype):
+        raise RuntimeError("cutlass_scaled_mm: bad bias")
+    # the slabs of a K split, sized as on the row-scaled path
+    if m <= 320:
+        ws = torch.empty((8, min(m, 64), n), dtype=torch.float32, device=a.device)
+    else:
+        elems = int(_abi.load().mi355x_scaled_mm_split_elems(m, n, k))
+        ws = _scratch_f32(elems, a.device) if elems else None
+    rc = _abi.load().mi355x_scaled_mm_fp8_block(
+        _ptr(out), _ptr(a), _ptr(b), _ptr(a_scales), a_scales.stride(0), a_scales.stride(1), _ptr(b_scales),
+        b_scales.stride(0), b_scales.stride(1), _ptr(bias), _ptr(ws), ws.numel() if ws is not None else 0, m, n, k,
+        a.stride(0), b.stride(1), out.stride(0), _dt(out), _stream())
+    _abi.check(rc, "cutlass_scaled_mm")
+
+
+def per_token_group_quant_fp8(x: torch.Tensor, group_size: int = 128, column_major_scales: bool = False,
+                              eps: float = 1e-10):
+    """(q, scales): x [..., hidden] f16 / bf16 quantised to e4m3fn per token and `group_size`-wide group, scales
+    float32 [tokens, hidden / group_size] = max(absmax, eps) / 448 — token-contiguous (the transpose of a
+    [groups, tokens] tensor) when `column_major_scales`.  The activation side of the block-scaled cutlass_scaled_mm."""
+    _dev(x)
+    if x.stride(-1) != 1:
+        raise RuntimeError("per_token_group_quant_fp8: last dimension must be contiguous")
+    x2 = x.reshape(-1, x.shape[-1])
+    tokens, hidden = x2.shape
+    groups = hidden // group_size if group_size > 0 else 0
+    q = torch.empty((tokens, hidden), dtype=torch.float8_e4m3fn, device=x.device)
+    if column_major_scales:
+        scales = torch.empty((groups, tokens), dtype=torch.float32, device=x.device).t()
+    else:
+        scales = torch.empty((tokens, groups), dtype=torch.float32, device=x.device)
+    rc = _abi.load().mi355x_per_token_group_fp8_quant(
+        _ptr(q), _ptr(scales), _ptr(x2), tokens, hidden, group_size, x2.stride(0), q.stride(0), scales.stride(0),
+        scales.stride(1), eps, _dt(x2), _stream())
+    _abi.check(rc, "per_token_group_quant_fp8")
+    return q.reshape(x.shape), scales
+
+
 def cutlass_scaled_mm(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
                       a_scales: torch.Tensor, b_scales: torch.Tensor,
                       bias: Optional[torch.Tensor] = None) -> None:
@@ -1343,6 +1402,10 @@ def cutlass_scaled_mm(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     m, k = a.shape
     n = b.size(1)
     if a_scales.numel() not in (1, m) or b_scales.numel() not in (1, n):
+        # block-scaled fp8: one scale per token and 128-wide K group, one per 128 x 128 weight block
+        if a.dtype == torch.float8_e4m3fn and k % 128 == 0 and tuple(a_scales.shape) == (m, k // 128) \
+                and tuple(b_scales.shape) == (k // 128, (n + 127) // 128):
+            return _scaled_mm_fp8_block(out, a, b, a_scales, b_scales, bias)
         raise RuntimeError("cutlass_scaled_mm: scales must be per-tensor or per-row/column")
     if a_scales.dtype != torch.float32 or b_scales.dtype != torch.float32:
         raise RuntimeError("cutlass_scaled_mm: scales must be float32")

@@ -6,6 +6,7 @@
 //   dynamic:  scale = max over tensor of absmax(row)/448, folded with an atomic max
 //             into a caller-zeroed scalar; then q = sat( float(x) * (1/scale) )
 //   per-tok:  s = max( min(absmax, ub)/448, 1/(448*512) ); q = sat( float(x) / s )
+//   per-tok-group (128): s = max(absmax of the group, eps)/448; q = sat( float(x) / s )  (block-scaled GEMM input)
 // sat() clamps to +-448 and converts RNE (v_cvt_pk_fp8_f32, OCP e4m3fn on gfx950).
 // One workgroup per token row, 16-B loads / 8-B stores when the row is aligned.
 #include "common.cuh"
@@ -108,6 +109,39 @@ __global__ void per_token_fp8_quant_kernel(uint8_t* __restrict__ out,
   quant_row<T, VEC, true>(out + row * out_stride, rin, hidden, s_scale);
 }
 
+// per token and 128-wide group: s = max(absmax, eps) / 448, q = sat(x / s) — the activation side of the block-scaled
+// GEMM (fp8_block_gemm.hip).  One workgroup per token, 16 bytes = 8 elements per lane, so a group is 16 adjacent lanes
+// of one wave: its absmax is four butterfly steps, no LDS.  The division is the exact three-operation row division of
+// the per-token kernel (common.cuh), with the group's scale as the divisor.
+template <typename T>
+__global__ void per_token_group_fp8_quant_kernel(uint8_t* __restrict__ out, float* __restrict__ scales,
+                                                 const T* __restrict__ in, int hidden, int64_t in_stride,
+                                                 int64_t out_stride, int64_t scale_row_stride,
+                                                 int64_t scale_group_stride, float eps) {
+  static_assert(sizeof(T) == 2, "8 elements per 16-byte load");
+  const int64_t row = blockIdx.x;
+  const T* rin = in + row * in_stride;
+  for (int i = threadIdx.x * 8; i < hidden; i += blockDim.x * 8) {   // (whole groups: hidden % 128 == 0)
+    T v[8];
+    float x[8], y[8];
+    *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(rin + i);
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x[j] = to_f32(v[j]);
+      amax = fmaxf(amax, fabsf(x[j]));
+    }
+#pragma unroll
+    for (int mask = 8; mask >= 1; mask >>= 1) amax = fmaxf(amax, __shfl_xor(amax, mask, 64));
+    const float s = fmaxf(amax, eps) / kFp8Max;
+    if ((threadIdx.x & 15) == 0) scales[row * scale_row_stride + (i >> 7) * scale_group_stride] = s;
+    const RowDiv rdiv = make_row_div(s);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = row_div(x[j], rdiv);
+    *reinterpret_cast<uint2*>(out + row * out_stride + i) = f32x8_to_fp8x8_sat(y);
+  }
+}
+
 template <typename T>
 static bool row_vec_ok(const void* in, const void* out, int hidden, int64_t in_stride,
                        int64_t out_stride) {
@@ -206,6 +240,34 @@ int mi355x_dynamic_per_token_scaled_fp8_quant(void* out, const void* input,
       hipLaunchKernelGGL((per_token_fp8_quant_kernel<scalar_t, false>), grid, block, 0, s, o,
                          scales, in, scale_ub, hidden_size, in_row_stride, out_row_stride);
     return check_launch("dynamic_per_token_scaled_fp8_quant");
+  });
+}
+
+int mi355x_per_token_group_fp8_quant(void* out, float* scales, const void* input, int num_tokens,
+                                     int hidden_size, int group_size, int64_t in_row_stride,
+                                     int64_t out_row_stride, int64_t scale_row_stride,
+                                     int64_t scale_group_stride, float eps, int dtype, mi355x_stream stream) {
+  MI355X_REQUIRE(num_tokens >= 0 && hidden_size > 0, MI355X_EINVAL, "per_token_group_fp8_quant: bad sizes");
+  MI355X_REQUIRE(group_size == 128, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant: group_size = %d, only 128 is supported", group_size);
+  MI355X_REQUIRE(hidden_size % 128 == 0, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant: hidden_size = %d must be a multiple of 128", hidden_size);
+  MI355X_REQUIRE(dtype == MI355X_F16 || dtype == MI355X_BF16, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant: input must be f16 or bf16");
+  MI355X_REQUIRE(in_row_stride % 8 == 0 && out_row_stride % 8 == 0 && in_row_stride >= hidden_size &&
+                     out_row_stride >= hidden_size && scale_row_stride >= 0 && scale_group_stride >= 0,
+                 MI355X_EUNSUPPORTED, "per_token_group_fp8_quant: row strides must be multiples of 8 elements");
+  if (num_tokens == 0) return MI355X_OK;
+  MI355X_REQUIRE(out && scales && input, MI355X_EINVAL, "per_token_group_fp8_quant: null pointer");
+  MI355X_REQUIRE((reinterpret_cast<uintptr_t>(input) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+                 MI355X_EUNSUPPORTED, "per_token_group_fp8_quant: input must be 16-byte, out 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return MI355X_DISPATCH_HALF(dtype, [&] {
+    hipLaunchKernelGGL((per_token_group_fp8_quant_kernel<scalar_t>), dim3(num_tokens),
+                       dim3(row_threads(hidden_size, 8)), 0, s, static_cast<uint8_t*>(out), scales,
+                       static_cast<const scalar_t*>(input), hidden_size, in_row_stride, out_row_stride,
+                       scale_row_stride, scale_group_stride, eps);
+    return check_launch("per_token_group_fp8_quant");
   });
 }
 

@@ -424,14 +424,35 @@ void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tens
   TORCH_CHECK(a.scalar_type() == b.scalar_type() && (is_i8 || a.scalar_type() == at::kFloat8_e4m3fn),
               "cutlass_scaled_mm: a and b must both be int8 or both float8_e4m3fn");
   const int64_t m = a.size(0), k = a.size(1), n = b.size(1);
-  TORCH_CHECK(a_scales.numel() == 1 || a_scales.numel() == m);
-  TORCH_CHECK(b_scales.numel() == 1 || b_scales.numel() == n);
-  TORCH_CHECK(a_scales.is_contiguous() && b_scales.is_contiguous());
   TORCH_CHECK(a_scales.scalar_type() == at::kFloat && b_scales.scalar_type() == at::kFloat);
   if (bias.has_value() && bias->defined()) {
     TORCH_CHECK(bias->numel() == n && bias->is_contiguous() && bias->dim() == 1 &&
                 bias->scalar_type() == out.scalar_type());
   }
+  const bool plain = (a_scales.numel() == 1 || a_scales.numel() == m) && (b_scales.numel() == 1 || b_scales.numel() == n);
+  if (!plain) {
+    // block-scaled fp8 (fp8_block_gemm.hip): a_scales [m, k / 128], b_scales [k / 128, ceil(n / 128)], any strides —
+    // only shapes the per-tensor / per-row / per-column rule above refuses come here
+    const int64_t kb = k / 128, nb = (n + 127) / 128;
+    TORCH_CHECK(!is_i8 && k % 128 == 0 && a_scales.dim() == 2 && b_scales.dim() == 2 && a_scales.size(0) == m &&
+                    a_scales.size(1) == kb && b_scales.size(0) == kb && b_scales.size(1) == nb,
+                "cutlass_scaled_mm: scales must be per-tensor or per-row/column, or (fp8) per 128-wide group "
+                "[m, k / 128] and per 128 x 128 block [k / 128, ceil(n / 128)]");
+    Guard g(a);
+    Tensor ws;   // slabs of a K split, sized as on the row-scaled path below
+    if (m <= 320 && m > 0) ws = at::empty({8, m < 64 ? m : 64, n}, a.options().dtype(at::kFloat));
+    else if (const int64_t elems = mi355x_scaled_mm_split_elems((int)m, (int)n, (int)k))
+      ws = at::empty({elems}, a.options().dtype(at::kFloat));
+    ok(mi355x_scaled_mm_fp8_block(out.data_ptr(), a.data_ptr(), b.data_ptr(), a_scales.data_ptr<float>(),
+                                  a_scales.stride(0), a_scales.stride(1), b_scales.data_ptr<float>(),
+                                  b_scales.stride(0), b_scales.stride(1),
+                                  (bias.has_value() && bias->defined()) ? bias->data_ptr() : nullptr,
+                                  ws.defined() ? ws.data_ptr<float>() : nullptr, ws.defined() ? ws.numel() : 0, m, n,
+                                  k, a.stride(0), b.stride(1), out.stride(0), dt(out), stream_of(a)),
+       "cutlass_scaled_mm");
+    return;
+  }
+  TORCH_CHECK(a_scales.is_contiguous() && b_scales.is_contiguous());
   Guard g(a);
   Tensor ws;  // small-M (decode) shapes split K across up to 8 workgroups, one 4-byte partial slab [m, n] each
   // (64 < m <= 320: passes of 64 rows through the decode kernel; above: the packed-image kernel)
@@ -460,6 +481,8 @@ void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tens
 }
 
 bool cutlass_scaled_mm_supports_fp8(int64_t cuda_device_capability) { return true; }
+// the reference answers false (torch_bindings.cpp:273-278); here the block form of cutlass_scaled_mm above
+bool cutlass_scaled_mm_supports_block_fp8(int64_t cuda_device_capability) { return true; }
 
 // ------------------------------------------------------------------ int8 quant
 // ref: csrc/quantization/compressed_tensors/int8_quant_kernels.cu (launchers), schema
@@ -518,6 +541,27 @@ void dynamic_per_token_scaled_fp8_quant(Tensor& out, const Tensor& input, Tensor
                                                rows(input), input.size(-1), row_stride(input),
                                                row_stride(out), dt(input), stream_of(input)),
      "dynamic_per_token_scaled_fp8_quant");
+}
+
+// upstream vLLM's schema of the group quantiser; output_s [tokens, groups] with any strides (the token-contiguous
+// "column-major scales" included).  fp8_min / fp8_max must be the e4m3fn range the kernel saturates to.
+void per_token_group_fp8_quant(const Tensor& input, Tensor& output_q, Tensor& output_s, int64_t group_size,
+                               double eps, double fp8_min, double fp8_max, bool scale_ue8m0) {
+  TORCH_CHECK(!scale_ue8m0, "per_token_group_fp8_quant: UE8M0 scales are not implemented");
+  TORCH_CHECK(fp8_max == 448.0 && fp8_min == -448.0, "per_token_group_fp8_quant: e4m3fn range (+-448) only");
+  TORCH_CHECK(input.dim() == 2 && output_q.dim() == 2 && output_s.dim() == 2 && input.stride(1) == 1 &&
+                  output_q.stride(1) == 1 && output_q.sizes() == input.sizes(),
+              "per_token_group_fp8_quant: 2-D tensors with a contiguous last dimension");
+  check_fp8(output_q);
+  TORCH_CHECK(output_s.scalar_type() == at::kFloat && output_s.size(0) == input.size(0) && group_size > 0 &&
+                  output_s.size(1) * group_size == input.size(1),
+              "per_token_group_fp8_quant: output_s must be float32 [tokens, hidden / group_size]");
+  Guard g(input);
+  ok(mi355x_per_token_group_fp8_quant(output_q.data_ptr(), output_s.data_ptr<float>(), input.data_ptr(),
+                                      input.size(0), input.size(1), (int)group_size, input.stride(0),
+                                      output_q.stride(0), output_s.stride(0), output_s.stride(1), (float)eps,
+                                      dt(input), stream_of(input)),
+     "per_token_group_fp8_quant");
 }
 
 // ------------------------------------------------------------------- cache ops
@@ -747,6 +791,9 @@ TORCH_LIBRARY(_C, ops) {
   ops.def("cutlass_scaled_mm_supports_fp8(int cuda_device_capability) -> bool");
   ops.impl("cutlass_scaled_mm_supports_fp8", &cutlass_scaled_mm_supports_fp8);
 
+  ops.def("cutlass_scaled_mm_supports_block_fp8(int cuda_device_capability) -> bool");
+  ops.impl("cutlass_scaled_mm_supports_block_fp8", &cutlass_scaled_mm_supports_block_fp8);
+
   ops.def(
       "gptq_gemm(Tensor a, Tensor b_q_weight, Tensor b_gptq_qzeros, "
       "Tensor b_gptq_scales, Tensor b_g_idx, bool use_exllama, int bit, int "
@@ -768,6 +815,11 @@ TORCH_LIBRARY(_C, ops) {
       "Tensor! scale, Tensor? scale_ub) -> ()");
   ops.impl("dynamic_per_token_scaled_fp8_quant", c10::kCUDA,
            &dynamic_per_token_scaled_fp8_quant);
+
+  ops.def(
+      "per_token_group_fp8_quant(Tensor input, Tensor! output_q, Tensor! output_s, int group_size, "
+      "float eps, float fp8_min, float fp8_max, bool scale_ue8m0) -> ()");
+  ops.impl("per_token_group_fp8_quant", c10::kCUDA, &per_token_group_fp8_quant);
 }
 
 TORCH_LIBRARY(_C_cache_ops, cache_ops) {

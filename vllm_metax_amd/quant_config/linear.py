@@ -106,6 +106,23 @@ def apply_awq_fake(x, qweight, scales, qzeros, bias, pack_factor, group_size):
     return torch.empty(x.shape[:-1] + (n,), dtype=x.dtype, device=x.device)
 
 
+def apply_fp8_block(x: torch.Tensor, weight: torch.Tensor, weight_scale_inv: torch.Tensor,
+                    bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """Linear on a block-quantised fp8 checkpoint layer (weight_block_size = [128, 128]): `weight` e4m3fn [n, k],
+    `weight_scale_inv` float32 [ceil(n / 128), k / 128].  The activations are quantised per token and 128-wide group
+    on the fly; weight and scales go to the GEMM as transposed views, without a copy."""
+    reshaped_x = x.reshape(-1, x.shape[-1])
+    n = weight.shape[0]
+    q, s = ops.per_token_group_quant_fp8(reshaped_x, 128)
+    out = torch.empty((reshaped_x.shape[0], n), dtype=x.dtype, device=x.device)
+    ops.cutlass_scaled_mm(out, q, weight.t(), s, weight_scale_inv.t(), bias)
+    return out.reshape(x.shape[:-1] + (n,))
+
+
+def apply_fp8_block_fake(x, weight, weight_scale_inv, bias):
+    return torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=x.dtype, device=x.device)
+
+
 def gptq_process_weights(qweight: torch.Tensor, g_idx: torch.Tensor, desc_act: bool,
                          weight_bits: int) -> torch.Tensor:
     """ref: gptq.py:49-75 — argsort g_idx when act-order, then exllama shuffle in place.
