@@ -640,6 +640,39 @@ enum {
 };
 int mi355x_scaled_mm_block_last_route(void);
 
+/* MX-FP4 (OCP microscaling, w4a4) GEMM (csrc/mxfp4_gemm.hip): e2m1 nibbles (sign in bit 3, codes 0..7 = 0, 0.5, 1,
+ * 1.5, 2, 3, 4, 6; byte j of a row = element 2 j in the low nibble, 2 j + 1 in the high one) with one E8M0 scale byte
+ * (2^(s - 127); 255 is outside the contract) per 32-wide K group on both operands, applied inside the scaled MFMA:
+ *   out[i, j] = T( sum_g 2^(a_s[i, g] - 127) 2^(b_s[g, j] - 127) (sum_{kk in group g} a[i, kk] b[kk, j]) + bias[j] )
+ * a [m, k / 2] bytes row-major, b [k / 2, n] column-major (lda, ldb in BYTES), a_scales[i * a_s_row_stride + g],
+ * b_scales[j * b_s_col_stride + g] (a checkpoint's [n, k / 32] tensor as it is).  Requires k % 128 == 0, n % 16 == 0,
+ * a, b, out 16-byte aligned, lda, ldb, ldc * sizeof(T) multiples of 16 bytes, the scales and their row strides
+ * multiples of 4 bytes; anything else returns MI355X_EUNSUPPORTED.  `workspace` (fp32 elements, 16-byte
+ * aligned, may be NULL): mi355x_scaled_mm_mxfp4_workspace_elems(m, n, k) elements let either kernel split K; slabs
+ * are added in order by a finish launch (no memset, no atomics: HIP-graph-replayable). */
+int mi355x_scaled_mm_mxfp4(void* out, const void* a, const void* b, const void* a_scales, int64_t a_s_row_stride,
+                           const void* b_scales, int64_t b_s_col_stride, const void* bias, float* workspace,
+                           int64_t workspace_elems, int m, int n, int k, int64_t lda, int64_t ldb, int64_t ldc,
+                           int out_dtype, mi355x_stream stream);
+/* The kernels the most recent mi355x_scaled_mm_mxfp4 on the calling thread launched; the entry clears the mask. */
+enum {
+  MI355X_MX4_ROUTE_STREAM = 1,     /* mx4_stream_kernel: m <= 65, passes of 64 rows                             */
+  MI355X_MX4_ROUTE_TILE = 2,       /* mx4_tile_kernel: the 256 x 256 tile kernel                                */
+  MI355X_MX4_ROUTE_SUM_SLABS = 4   /* K was split: fp32 slabs added by mx4_finish_kernel                        */
+};
+int mi355x_scaled_mm_mxfp4_last_route(void);
+/* The fp32 workspace elements mi355x_scaled_mm_mxfp4 can use at this shape (0: none): the slabs of the kernel its
+ * router takes. */
+int64_t mi355x_scaled_mm_mxfp4_workspace_elems(int m, int n, int k);
+/* The activation side: per token and 32-wide group, with amax in fp32,
+ *   e = ((bits(amax) + 0x200000) >> 23) & 0xFF,  s = clamp(e - 2, 0, 254),  q = sat_rne_e2m1(x * 2^(127 - s))
+ * (ties to the even code, |v| > 5 -> 6, the nibble's sign is x's sign bit): the rounded-amax rule of AMD's dynamic
+ * MXFP4 quantisation.  out_q [num_tokens, hidden_size / 2] bytes, out_s [num_tokens, hidden_size / 32] bytes, row
+ * strides in elements (input) and bytes (q, s); f16 / bf16 input, hidden_size % 32 == 0. */
+int mi355x_per_token_group_mxfp4_quant(void* out_q, void* out_s, const void* input, int num_tokens, int hidden_size,
+                                       int64_t in_row_stride, int64_t q_row_stride, int64_t s_row_stride, int dtype,
+                                       mi355x_stream stream);
+
 /* Shapes with few 256 x 256 output tiles (chunked-prefill sized m, the narrow n of a TP shard) split K inside the
  * m > 320 kernel when the workspace has room for the partial tiles: mi355x_scaled_mm_split_elems returns the 4-byte
  * elements to ADD to the operand-image scratch above for that (0: this shape is not split).  Without them the GEMM

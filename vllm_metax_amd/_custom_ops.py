@@ -1382,6 +1382,63 @@ def per_token_group_quant_fp8(x: torch.Tensor, group_size: int = 128, column_maj
     return q.reshape(x.shape), scales
 
 
+# MI355X_MX4_ROUTE_* (include/mi355x_hotpath.h): the bits of scaled_mm_mxfp4_last_route()
+MX4_ROUTE_STREAM, MX4_ROUTE_TILE, MX4_ROUTE_SUM_SLABS = 1, 2, 4
+
+
+def scaled_mm_mxfp4_last_route() -> int:
+    """Mask of the kernels the most recent MX-FP4 cutlass_scaled_mm on this thread launched."""
+    return int(_abi.load().mi355x_scaled_mm_mxfp4_last_route())
+
+
+def _scaled_mm_mxfp4(out, a, b, a_scales, b_scales, bias) -> None:
+    """cutlass_scaled_mm on MX-FP4 operands (mxfp4_gemm.hip): a [m, k / 2] and b [k / 2, n] float4_e2m1fn_x2 (two
+    nibbles per byte), a_scales [m, k / 32] and b_scales [k / 32, n] float8_e8m0fnu with the group index contiguous —
+    a checkpoint's [n, k / 2] weight and [n, k / 32] scale go in as their .t()."""
+    m, k = a.size(0), a.size(1) * 2
+    n = b.size(1)
+    e8 = torch.float8_e8m0fnu
+    if k % 128:
+        raise RuntimeError("cutlass_scaled_mm: MX-FP4 needs k % 128 == 0")
+    if a_scales.dtype != e8 or b_scales.dtype != e8:
+        raise RuntimeError("cutlass_scaled_mm: MX-FP4 scales must be float8_e8m0fnu")
+    if tuple(a_scales.shape) != (m, k // 32) or tuple(b_scales.shape) != (k // 32, n):
+        raise RuntimeError("cutlass_scaled_mm: MX-FP4 scales must be [m, k / 32] and [k / 32, n]")
+    if a_scales.stride(1) != 1 or b_scales.stride(0) != 1:
+        raise RuntimeError("cutlass_scaled_mm: MX-FP4 scales must be contiguous along the K groups")
+    if bias is not None and (bias.numel() != n or not bias.is_contiguous() or bias.dtype != out.dtype):
+        raise RuntimeError("cutlass_scaled_mm: bad bias")
+    # the slabs of a K split, for the kernel the router takes at this shape
+    elems = int(_abi.load().mi355x_scaled_mm_mxfp4_workspace_elems(m, n, k))
+    ws = torch.empty(elems, dtype=torch.float32, device=a.device) if elems else None
+    rc = _abi.load().mi355x_scaled_mm_mxfp4(
+        _ptr(out), _ptr(a), _ptr(b), _ptr(a_scales), a_scales.stride(0), _ptr(b_scales), b_scales.stride(1),
+        _ptr(bias), _ptr(ws), ws.numel() if ws is not None else 0, m, n, k, a.stride(0), b.stride(1), out.stride(0),
+        _dt(out), _stream())
+    _abi.check(rc, "cutlass_scaled_mm")
+
+
+def per_token_group_quant_mxfp4(x: torch.Tensor):
+    """(q, scales): x [..., hidden] f16 / bf16 quantised to MX-FP4 per token and 32-wide group — q [..., hidden / 2]
+    float4_e2m1fn_x2, scales [tokens, hidden / 32] float8_e8m0fnu by the rounded-amax rule (mxfp4_gemm.hip).  The
+    activation side of the MX-FP4 cutlass_scaled_mm."""
+    _dev(x)
+    if x.stride(-1) != 1:
+        raise RuntimeError("per_token_group_quant_mxfp4: last dimension must be contiguous")
+    if x.shape[-1] % 32:
+        raise RuntimeError("per_token_group_quant_mxfp4: hidden must be a multiple of 32")
+    x2 = x.reshape(-1, x.shape[-1])
+    tokens, hidden = x2.shape
+    q = torch.empty((tokens, hidden // 2), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((tokens, hidden // 32), dtype=torch.uint8, device=x.device)
+    rc = _abi.load().mi355x_per_token_group_mxfp4_quant(
+        _ptr(q), _ptr(scales), _ptr(x2), tokens, hidden, x2.stride(0), q.stride(0), scales.stride(0), _dt(x2),
+        _stream())
+    _abi.check(rc, "per_token_group_quant_mxfp4")
+    return (q.view(torch.float4_e2m1fn_x2).reshape(x.shape[:-1] + (hidden // 2,)),
+            scales.view(torch.float8_e8m0fnu))
+
+
 def cutlass_scaled_mm(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
                       a_scales: torch.Tensor, b_scales: torch.Tensor,
                       bias: Optional[torch.Tensor] = None) -> None:
@@ -1397,8 +1454,11 @@ def cutlass_scaled_mm(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
         raise RuntimeError("cutlass_scaled_mm: b must be column-major")
     if out.stride(0) % 16 or b.stride(1) % 16:
         raise RuntimeError("cutlass_scaled_mm: 16-byte alignment required")
+    if a.dtype == torch.float4_e2m1fn_x2 and b.dtype == torch.float4_e2m1fn_x2:
+        return _scaled_mm_mxfp4(out, a, b, a_scales, b_scales, bias)
     if a.dtype != b.dtype or a.dtype not in (torch.float8_e4m3fn, torch.int8):
-        raise RuntimeError("cutlass_scaled_mm: a and b must both be float8_e4m3fn or both int8")
+        raise RuntimeError("cutlass_scaled_mm: a and b must both be float8_e4m3fn, both int8 or both "
+                           "float4_e2m1fn_x2")
     m, k = a.shape
     n = b.size(1)
     if a_scales.numel() not in (1, m) or b_scales.numel() not in (1, n):

@@ -420,9 +420,35 @@ void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tens
   TORCH_CHECK(a.stride(1) == 1 && out.stride(1) == 1);  // row-major
   TORCH_CHECK(b.stride(0) == 1);                         // column-major
   TORCH_CHECK(out.stride(0) % 16 == 0 && b.stride(1) % 16 == 0);
+  if (a.scalar_type() == at::kFloat4_e2m1fn_x2 && b.scalar_type() == at::kFloat4_e2m1fn_x2) {
+    // MX-FP4 (mxfp4_gemm.hip): two nibbles per byte, E8M0 scales [m, k / 32] and [k / 32, n], K groups contiguous
+    const int64_t m = a.size(0), k = a.size(1) * 2, n = b.size(1);
+    TORCH_CHECK(k % 128 == 0, "cutlass_scaled_mm: MX-FP4 needs k % 128 == 0");
+    TORCH_CHECK(a_scales.scalar_type() == at::kFloat8_e8m0fnu && b_scales.scalar_type() == at::kFloat8_e8m0fnu &&
+                    a_scales.dim() == 2 && b_scales.dim() == 2 && a_scales.size(0) == m &&
+                    a_scales.size(1) == k / 32 && b_scales.size(0) == k / 32 && b_scales.size(1) == n &&
+                    a_scales.stride(1) == 1 && b_scales.stride(0) == 1,
+                "cutlass_scaled_mm: MX-FP4 scales must be float8_e8m0fnu [m, k / 32] and [k / 32, n], contiguous "
+                "along the K groups");
+    const bool has_bias = bias.has_value() && bias->defined();
+    if (has_bias) {
+      TORCH_CHECK(bias->numel() == n && bias->is_contiguous() && bias->dim() == 1 &&
+                  bias->scalar_type() == out.scalar_type());
+    }
+    Guard g(a);
+    Tensor ws;   // slabs of a K split, for the kernel the router takes at this shape
+    if (const int64_t elems = mi355x_scaled_mm_mxfp4_workspace_elems((int)m, (int)n, (int)k))
+      ws = at::empty({elems}, out.options().dtype(at::kFloat));
+    ok(mi355x_scaled_mm_mxfp4(out.data_ptr(), a.data_ptr(), b.data_ptr(), a_scales.data_ptr(), a_scales.stride(0),
+                              b_scales.data_ptr(), b_scales.stride(1), has_bias ? bias->data_ptr() : nullptr,
+                              ws.defined() ? ws.data_ptr<float>() : nullptr, ws.defined() ? ws.numel() : 0, m, n, k,
+                              a.stride(0), b.stride(1), out.stride(0), dt(out), stream_of(a)),
+       "cutlass_scaled_mm");
+    return;
+  }
   const bool is_i8 = a.scalar_type() == at::kChar;
   TORCH_CHECK(a.scalar_type() == b.scalar_type() && (is_i8 || a.scalar_type() == at::kFloat8_e4m3fn),
-              "cutlass_scaled_mm: a and b must both be int8 or both float8_e4m3fn");
+              "cutlass_scaled_mm: a and b must both be int8, both float8_e4m3fn or both float4_e2m1fn_x2");
   const int64_t m = a.size(0), k = a.size(1), n = b.size(1);
   TORCH_CHECK(a_scales.scalar_type() == at::kFloat && b_scales.scalar_type() == at::kFloat);
   if (bias.has_value() && bias->defined()) {
@@ -562,6 +588,25 @@ void per_token_group_fp8_quant(const Tensor& input, Tensor& output_q, Tensor& ou
                                       output_q.stride(0), output_s.stride(0), output_s.stride(1), (float)eps,
                                       dt(input), stream_of(input)),
      "per_token_group_fp8_quant");
+}
+
+// the activation side of the MX-FP4 cutlass_scaled_mm: output_q [tokens, hidden / 2] float4_e2m1fn_x2 (or uint8),
+// output_s [tokens, hidden / 32] float8_e8m0fnu (or uint8)
+void per_token_group_mxfp4_quant(const Tensor& input, Tensor& output_q, Tensor& output_s) {
+  TORCH_CHECK(input.dim() == 2 && output_q.dim() == 2 && output_s.dim() == 2 && input.stride(1) == 1 &&
+                  output_q.stride(1) == 1 && output_s.stride(1) == 1 && input.size(1) % 32 == 0,
+              "per_token_group_mxfp4_quant: 2-D tensors with a contiguous last dimension, hidden % 32 == 0");
+  TORCH_CHECK(output_q.element_size() == 1 && output_q.size(0) == input.size(0) &&
+                  output_q.size(1) * 2 == input.size(1),
+              "per_token_group_mxfp4_quant: output_q must be one byte per element pair, [tokens, hidden / 2]");
+  TORCH_CHECK(output_s.element_size() == 1 && output_s.size(0) == input.size(0) &&
+                  output_s.size(1) * 32 == input.size(1),
+              "per_token_group_mxfp4_quant: output_s must be one byte per group, [tokens, hidden / 32]");
+  Guard g(input);
+  ok(mi355x_per_token_group_mxfp4_quant(output_q.data_ptr(), output_s.data_ptr(), input.data_ptr(), input.size(0),
+                                        input.size(1), input.stride(0), output_q.stride(0), output_s.stride(0),
+                                        dt(input), stream_of(input)),
+     "per_token_group_mxfp4_quant");
 }
 
 // ------------------------------------------------------------------- cache ops
@@ -820,6 +865,9 @@ TORCH_LIBRARY(_C, ops) {
       "per_token_group_fp8_quant(Tensor input, Tensor! output_q, Tensor! output_s, int group_size, "
       "float eps, float fp8_min, float fp8_max, bool scale_ue8m0) -> ()");
   ops.impl("per_token_group_fp8_quant", c10::kCUDA, &per_token_group_fp8_quant);
+
+  ops.def("per_token_group_mxfp4_quant(Tensor input, Tensor! output_q, Tensor! output_s) -> ()");
+  ops.impl("per_token_group_mxfp4_quant", c10::kCUDA, &per_token_group_mxfp4_quant);
 }
 
 TORCH_LIBRARY(_C_cache_ops, cache_ops) {

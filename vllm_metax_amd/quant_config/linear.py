@@ -123,6 +123,28 @@ def apply_fp8_block_fake(x, weight, weight_scale_inv, bias):
     return torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=x.dtype, device=x.device)
 
 
+def apply_mxfp4(x: torch.Tensor, weight: torch.Tensor, weight_scale: torch.Tensor,
+                bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """Linear on an MX-FP4 (w4a4) checkpoint layer: `weight` [n, k / 2] packed e2m1 nibbles, `weight_scale`
+    [n, k / 32] E8M0 bytes, either as uint8 (how checkpoints store them) or as float4_e2m1fn_x2 / float8_e8m0fnu.
+    The activations are quantised per token and 32-wide group on the fly; weight and scales go to the GEMM as
+    transposed views, without a copy."""
+    reshaped_x = x.reshape(-1, x.shape[-1])
+    n = weight.shape[0]
+    if weight.dtype == torch.uint8:
+        weight = weight.view(torch.float4_e2m1fn_x2)
+    if weight_scale.dtype == torch.uint8:
+        weight_scale = weight_scale.view(torch.float8_e8m0fnu)
+    q, s = ops.per_token_group_quant_mxfp4(reshaped_x)
+    out = torch.empty((reshaped_x.shape[0], n), dtype=x.dtype, device=x.device)
+    ops.cutlass_scaled_mm(out, q, weight.t(), s, weight_scale.t(), bias)
+    return out.reshape(x.shape[:-1] + (n,))
+
+
+def apply_mxfp4_fake(x, weight, weight_scale, bias):
+    return torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=x.dtype, device=x.device)
+
+
 def gptq_process_weights(qweight: torch.Tensor, g_idx: torch.Tensor, desc_act: bool,
                          weight_bits: int) -> torch.Tensor:
     """ref: gptq.py:49-75 — argsort g_idx when act-order, then exllama shuffle in place.
