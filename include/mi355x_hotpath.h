@@ -673,6 +673,43 @@ int mi355x_per_token_group_mxfp4_quant(void* out_q, void* out_s, const void* inp
                                        int64_t in_row_stride, int64_t q_row_stride, int64_t s_row_stride, int dtype,
                                        mi355x_stream stream);
 
+/* E8M0-scaled fp8 GEMM (csrc/fp8_e8m0_gemm.hip): e4m3fn operands whose scales are E8M0 bytes (2^(s - 127); 255 is
+ * outside the contract) on BOTH sides, applied inside the scaled MFMA — fp32 accumulation, one rounding:
+ *   out[i, j] = T( sum_g 2^(a_s[i, g] - 127) 2^(b_s[g, c(j)] - 127) (sum_{kk in group g} a[i, kk] b[kk, j]) + bias[j] )
+ * scale_group = 128 (block fp8 with ue8m0 scales): a_s [m, k / 128], b_s [k / 128, ceil(n / 128)], c(j) = j / 128, any
+ * non-negative strides.  scale_group = 32 (OCP MXFP8): a_s [m, k / 32], b_s [k / 32, n], c(j) = j, a_s_stride1 ==
+ * b_s_stride0 == 1, the other two strides and both pointers multiples of 4 bytes.  Scales are addressed
+ * a_scales[i * a_s_stride0 + g * a_s_stride1], b_scales[g * b_s_stride0 + c * b_s_stride1].  a [m, k] row-major, b
+ * [k, n] column-major; k % 128 == 0, n % 16 == 0, a, b, out 16-byte aligned, lda, ldb, ldc * sizeof(T) multiples of
+ * 16 bytes; anything else returns MI355X_EUNSUPPORTED before any launch.  `workspace` (fp32 elements, 16-byte
+ * aligned, may be NULL): mi355x_scaled_mm_fp8_e8m0_workspace_elems(m, n, k) elements let either kernel split K; slabs
+ * are added in order by a finish launch (no memset, no atomics: HIP-graph-replayable). */
+int mi355x_scaled_mm_fp8_e8m0(void* out, const void* a, const void* b, const void* a_scales, int64_t a_s_stride0,
+                              int64_t a_s_stride1, const void* b_scales, int64_t b_s_stride0, int64_t b_s_stride1,
+                              const void* bias, float* workspace, int64_t workspace_elems, int m, int n, int k,
+                              int scale_group, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
+                              mi355x_stream stream);
+/* The kernels the most recent mi355x_scaled_mm_fp8_e8m0 on the calling thread launched; the entry clears this mask
+ * and leaves the one of mi355x_scaled_mm_block_last_route (the fp32-scaled entry's) as it was. */
+enum {
+  MI355X_F8E_ROUTE_STREAM = 1,     /* f8e_stream_kernel: m <= 65, passes of 64 rows                             */
+  MI355X_F8E_ROUTE_TILE = 2,       /* f8e_tile_kernel: the 256 x 256 tile kernel                                */
+  MI355X_F8E_ROUTE_SUM_SLABS = 4   /* K was split: fp32 slabs added by f8e_finish_kernel                        */
+};
+int mi355x_scaled_mm_fp8_e8m0_last_route(void);
+/* The fp32 workspace elements mi355x_scaled_mm_fp8_e8m0 can use at this shape (0: none). */
+int64_t mi355x_scaled_mm_fp8_e8m0_workspace_elems(int m, int n, int k);
+/* mi355x_per_token_group_fp8_quant with power-of-two (UE8M0) scales, group_size 32 or 128.  With s0 = max(absmax,
+ * eps) / 448 (the fp32 division):
+ *   byte = min((bits(s0) >> 23) + ((bits(s0) & 0x7FFFFF) != 0), 254)     — 2^ceil(log2 s0)
+ *   q = sat_rne_e4m3(x * 2^(127 - byte))                                 — the scaling is exact: one rounding
+ * scale_elem_size 1 stores the byte (float8_e8m0fnu, the input of mi355x_scaled_mm_fp8_e8m0), 4 the float
+ * 2^(byte - 127) (upstream's contract); strides of `scales` in elements, as in mi355x_per_token_group_fp8_quant. */
+int mi355x_per_token_group_fp8_quant_ue8m0(void* out, void* scales, int scale_elem_size, const void* input,
+                                           int num_tokens, int hidden_size, int group_size, int64_t in_row_stride,
+                                           int64_t out_row_stride, int64_t scale_row_stride,
+                                           int64_t scale_group_stride, float eps, int dtype, mi355x_stream stream);
+
 /* Shapes with few 256 x 256 output tiles (chunked-prefill sized m, the narrow n of a TP shard) split K inside the
  * m > 320 kernel when the workspace has room for the partial tiles: mi355x_scaled_mm_split_elems returns the 4-byte
  * elements to ADD to the operand-image scratch above for that (0: this shape is not split).  Without them the GEMM

@@ -114,6 +114,11 @@ PROTOTYPES = {
     "mi355x_scaled_mm_mxfp4_last_route": (_I, []),
     "mi355x_scaled_mm_mxfp4_workspace_elems": (_L, [_I, _I, _I]),
     "mi355x_per_token_group_mxfp4_quant": (_I, [_P, _P, _P, _I, _I, _L, _L, _L, _I, _P]),
+    "mi355x_scaled_mm_fp8_e8m0": (
+        _I, [_P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _P, _L, _I, _I, _I, _I, _L, _L, _L, _I, _P]),
+    "mi355x_scaled_mm_fp8_e8m0_last_route": (_I, []),
+    "mi355x_scaled_mm_fp8_e8m0_workspace_elems": (_L, [_I, _I, _I]),
+    "mi355x_per_token_group_fp8_quant_ue8m0": (_I, [_P, _P, _I, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P]),
     "mi355x_scaled_mm_prepack": (_I, [_P, _P, _I, _I, _L, _P]),
     "mi355x_scaled_mm_split_elems": (_L, [_I, _I, _I]),
     "mi355x_scaled_mm_prepacked": (

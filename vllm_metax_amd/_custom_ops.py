@@ -1360,26 +1360,81 @@ def _scaled_mm_fp8_block(out, a, b, a_scales, b_scales, bias) -> None:
 
 
 def per_token_group_quant_fp8(x: torch.Tensor, group_size: int = 128, column_major_scales: bool = False,
-                              eps: float = 1e-10):
+                              eps: float = 1e-10, scale_ue8m0: bool = False,
+                              scale_dtype: Optional[torch.dtype] = None):
     """(q, scales): x [..., hidden] f16 / bf16 quantised to e4m3fn per token and `group_size`-wide group, scales
     float32 [tokens, hidden / group_size] = max(absmax, eps) / 448 — token-contiguous (the transpose of a
-    [groups, tokens] tensor) when `column_major_scales`.  The activation side of the block-scaled cutlass_scaled_mm."""
+    [groups, tokens] tensor) when `column_major_scales`.  The activation side of the block-scaled cutlass_scaled_mm.
+    `scale_ue8m0`: the scale rounded up to a power of two (group_size 128 or 32; rule in fp8_quant.hip), returned as
+    float32 values or, with scale_dtype=torch.float8_e8m0fnu, as the bytes the E8M0-scaled cutlass_scaled_mm takes."""
     _dev(x)
     if x.stride(-1) != 1:
         raise RuntimeError("per_token_group_quant_fp8: last dimension must be contiguous")
+    scale_dtype = scale_dtype or torch.float32
+    if scale_dtype not in (torch.float32, torch.float8_e8m0fnu):
+        raise RuntimeError("per_token_group_quant_fp8: scale_dtype must be float32 or float8_e8m0fnu")
+    if scale_dtype != torch.float32 and not scale_ue8m0:
+        raise RuntimeError("per_token_group_quant_fp8: float8_e8m0fnu scales need scale_ue8m0=True")
     x2 = x.reshape(-1, x.shape[-1])
     tokens, hidden = x2.shape
     groups = hidden // group_size if group_size > 0 else 0
     q = torch.empty((tokens, hidden), dtype=torch.float8_e4m3fn, device=x.device)
     if column_major_scales:
-        scales = torch.empty((groups, tokens), dtype=torch.float32, device=x.device).t()
+        scales = torch.empty((groups, tokens), dtype=scale_dtype, device=x.device).t()
     else:
-        scales = torch.empty((tokens, groups), dtype=torch.float32, device=x.device)
-    rc = _abi.load().mi355x_per_token_group_fp8_quant(
-        _ptr(q), _ptr(scales), _ptr(x2), tokens, hidden, group_size, x2.stride(0), q.stride(0), scales.stride(0),
-        scales.stride(1), eps, _dt(x2), _stream())
+        scales = torch.empty((tokens, groups), dtype=scale_dtype, device=x.device)
+    if scale_ue8m0:
+        rc = _abi.load().mi355x_per_token_group_fp8_quant_ue8m0(
+            _ptr(q), _ptr(scales), scales.element_size(), _ptr(x2), tokens, hidden, group_size, x2.stride(0),
+            q.stride(0), scales.stride(0), scales.stride(1), eps, _dt(x2), _stream())
+    else:
+        rc = _abi.load().mi355x_per_token_group_fp8_quant(
+            _ptr(q), _ptr(scales), _ptr(x2), tokens, hidden, group_size, x2.stride(0), q.stride(0), scales.stride(0),
+            scales.stride(1), eps, _dt(x2), _stream())
     _abi.check(rc, "per_token_group_quant_fp8")
     return q.reshape(x.shape), scales
+
+
+# MI355X_F8E_ROUTE_* (include/mi355x_hotpath.h): the bits of scaled_mm_fp8_e8m0_last_route()
+F8E_ROUTE_STREAM, F8E_ROUTE_TILE, F8E_ROUTE_SUM_SLABS = 1, 2, 4
+
+
+def scaled_mm_fp8_e8m0_last_route() -> int:
+    """Mask of the kernels the most recent E8M0-scaled fp8 cutlass_scaled_mm on this thread launched."""
+    return int(_abi.load().mi355x_scaled_mm_fp8_e8m0_last_route())
+
+
+def _scaled_mm_fp8_e8m0(out, a, b, a_scales, b_scales, bias) -> None:
+    """cutlass_scaled_mm on e4m3 operands with float8_e8m0fnu scales (fp8_e8m0_gemm.hip).  The shape of the scales
+    chooses the form: [m, k / 128] and [k / 128, ceil(n / 128)] with any strides (block fp8 with ue8m0 scales), or
+    [m, k / 32] and [k / 32, n] contiguous along the K groups (MXFP8)."""
+    m, k = a.shape
+    n = b.size(1)
+    e8 = torch.float8_e8m0fnu
+    if a.dtype != torch.float8_e4m3fn or a_scales.dtype != e8 or b_scales.dtype != e8:
+        raise RuntimeError("cutlass_scaled_mm: float8_e8m0fnu scales need float8_e4m3fn operands and E8M0 on both "
+                           "sides")
+    if k % 128:
+        raise RuntimeError("cutlass_scaled_mm: E8M0 scales need k % 128 == 0")
+    if tuple(a_scales.shape) == (m, k // 128) and tuple(b_scales.shape) == (k // 128, (n + 127) // 128):
+        group = 128
+    elif tuple(a_scales.shape) == (m, k // 32) and tuple(b_scales.shape) == (k // 32, n):
+        group = 32
+        if a_scales.stride(1) != 1 or b_scales.stride(0) != 1:
+            raise RuntimeError("cutlass_scaled_mm: MXFP8 scales must be contiguous along the K groups")
+    else:
+        raise RuntimeError("cutlass_scaled_mm: E8M0 scales must be [m, k / 128] and [k / 128, ceil(n / 128)], or "
+                           "[m, k / 32] and [k / 32, n]")
+    if bias is not None and (bias.numel() != n or not bias.is_contiguous() or bias.dtype != out.dtype):
+        raise RuntimeError("cutlass_scaled_mm: bad bias")
+    # the slabs of a K split, for the kernel the router takes at this shape
+    elems = int(_abi.load().mi355x_scaled_mm_fp8_e8m0_workspace_elems(m, n, k))
+    ws = torch.empty(elems, dtype=torch.float32, device=a.device) if elems else None
+    rc = _abi.load().mi355x_scaled_mm_fp8_e8m0(
+        _ptr(out), _ptr(a), _ptr(b), _ptr(a_scales), a_scales.stride(0), a_scales.stride(1), _ptr(b_scales),
+        b_scales.stride(0), b_scales.stride(1), _ptr(bias), _ptr(ws), ws.numel() if ws is not None else 0, m, n, k,
+        group, a.stride(0), b.stride(1), out.stride(0), _dt(out), _stream())
+    _abi.check(rc, "cutlass_scaled_mm")
 
 
 # MI355X_MX4_ROUTE_* (include/mi355x_hotpath.h): the bits of scaled_mm_mxfp4_last_route()
@@ -1461,6 +1516,8 @@ def cutlass_scaled_mm(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
                            "float4_e2m1fn_x2")
     m, k = a.shape
     n = b.size(1)
+    if torch.float8_e8m0fnu in (a_scales.dtype, b_scales.dtype):
+        return _scaled_mm_fp8_e8m0(out, a, b, a_scales, b_scales, bias)
     if a_scales.numel() not in (1, m) or b_scales.numel() not in (1, n):
         # block-scaled fp8: one scale per token and 128-wide K group, one per 128 x 128 weight block
         if a.dtype == torch.float8_e4m3fn and k % 128 == 0 and tuple(a_scales.shape) == (m, k // 128) \

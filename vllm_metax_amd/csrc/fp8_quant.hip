@@ -7,6 +7,7 @@
 //             into a caller-zeroed scalar; then q = sat( float(x) * (1/scale) )
 //   per-tok:  s = max( min(absmax, ub)/448, 1/(448*512) ); q = sat( float(x) / s )
 //   per-tok-group (128): s = max(absmax of the group, eps)/448; q = sat( float(x) / s )  (block-scaled GEMM input)
+//   per-tok-group, UE8M0 (128 | 32): s = 2^ceil(log2(max(absmax, eps)/448)); q = sat( float(x) / s ), s as byte or float
 // sat() clamps to +-448 and converts RNE (v_cvt_pk_fp8_f32, OCP e4m3fn on gfx950).
 // One workgroup per token row, 16-B loads / 8-B stores when the row is aligned.
 #include "common.cuh"
@@ -142,6 +143,43 @@ __global__ void per_token_group_fp8_quant_kernel(uint8_t* __restrict__ out, floa
   }
 }
 
+// the same launch with power-of-two (UE8M0) scales — the activation side of fp8_e8m0_gemm.hip.  A group is GL = 16
+// (128 wide) or 4 (32 wide) adjacent lanes.  s0 = max(absmax, eps) / 448 as above, rounded UP to a power of two:
+// byte = exponent field + (mantissa != 0), at most 254, so |x| / 2^(byte - 127) <= 448; x * 2^(127 - byte) is exact,
+// the conversion its only rounding.  S = uint8_t stores the byte, S = float the value 2^(byte - 127).
+template <typename T, typename S, int GL>
+__global__ void per_token_group_fp8_quant_ue8m0_kernel(uint8_t* __restrict__ out, S* __restrict__ scales,
+                                                       const T* __restrict__ in, int hidden, int64_t in_stride,
+                                                       int64_t out_stride, int64_t scale_row_stride,
+                                                       int64_t scale_group_stride, float eps) {
+  static_assert(sizeof(T) == 2, "8 elements per 16-byte load");
+  const int64_t row = blockIdx.x;
+  const T* rin = in + row * in_stride;
+  for (int i = threadIdx.x * 8; i < hidden; i += blockDim.x * 8) {   // (whole groups: hidden % (8 GL) == 0)
+    T v[8];
+    float x[8], y[8];
+    *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(rin + i);
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      x[j] = to_f32(v[j]);
+      amax = fmaxf(amax, fabsf(x[j]));
+    }
+#pragma unroll
+    for (int mask = GL / 2; mask >= 1; mask >>= 1) amax = fmaxf(amax, __shfl_xor(amax, mask, 64));
+    const uint32_t bits = __float_as_uint(fmaxf(amax, eps) / kFp8Max);
+    const int byte = min((int)(bits >> 23) + ((bits & 0x7FFFFFu) != 0), 254);
+    if ((threadIdx.x & (GL - 1)) == 0) {
+      S* dst = scales + row * scale_row_stride + (i / (8 * GL)) * scale_group_stride;
+      if constexpr (sizeof(S) == 1) *dst = (uint8_t)byte;
+      else *dst = __uint_as_float(byte ? (uint32_t)byte << 23 : 0x00400000u);   // (2^-127 is subnormal)
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = __builtin_ldexpf(x[j], 127 - byte);
+    *reinterpret_cast<uint2*>(out + row * out_stride + i) = f32x8_to_fp8x8_sat(y);
+  }
+}
+
 template <typename T>
 static bool row_vec_ok(const void* in, const void* out, int hidden, int64_t in_stride,
                        int64_t out_stride) {
@@ -268,6 +306,47 @@ int mi355x_per_token_group_fp8_quant(void* out, float* scales, const void* input
                        static_cast<const scalar_t*>(input), hidden_size, in_row_stride, out_row_stride,
                        scale_row_stride, scale_group_stride, eps);
     return check_launch("per_token_group_fp8_quant");
+  });
+}
+
+int mi355x_per_token_group_fp8_quant_ue8m0(void* out, void* scales, int scale_elem_size, const void* input,
+                                           int num_tokens, int hidden_size, int group_size, int64_t in_row_stride,
+                                           int64_t out_row_stride, int64_t scale_row_stride,
+                                           int64_t scale_group_stride, float eps, int dtype, mi355x_stream stream) {
+  MI355X_REQUIRE(num_tokens >= 0 && hidden_size > 0, MI355X_EINVAL, "per_token_group_fp8_quant(ue8m0): bad sizes");
+  MI355X_REQUIRE(group_size == 128 || group_size == 32, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant(ue8m0): group_size = %d, only 128 and 32 are supported", group_size);
+  MI355X_REQUIRE(scale_elem_size == 1 || scale_elem_size == 4, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant(ue8m0): scales must be bytes or float32");
+  MI355X_REQUIRE(hidden_size % group_size == 0, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant(ue8m0): hidden_size = %d must be a multiple of %d", hidden_size,
+                 group_size);
+  MI355X_REQUIRE(dtype == MI355X_F16 || dtype == MI355X_BF16, MI355X_EUNSUPPORTED,
+                 "per_token_group_fp8_quant(ue8m0): input must be f16 or bf16");
+  MI355X_REQUIRE(in_row_stride % 8 == 0 && out_row_stride % 8 == 0 && in_row_stride >= hidden_size &&
+                     out_row_stride >= hidden_size && scale_row_stride >= 0 && scale_group_stride >= 0,
+                 MI355X_EUNSUPPORTED, "per_token_group_fp8_quant(ue8m0): row strides must be multiples of 8 elements");
+  if (num_tokens == 0) return MI355X_OK;
+  MI355X_REQUIRE(out && scales && input, MI355X_EINVAL, "per_token_group_fp8_quant(ue8m0): null pointer");
+  MI355X_REQUIRE((reinterpret_cast<uintptr_t>(input) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+                 MI355X_EUNSUPPORTED, "per_token_group_fp8_quant(ue8m0): input must be 16-byte, out 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return MI355X_DISPATCH_HALF(dtype, [&] {
+    auto launch = [&](auto kern, auto* sc) {
+      hipLaunchKernelGGL(kern, dim3(num_tokens), dim3(row_threads(hidden_size, 8)), 0, s, static_cast<uint8_t*>(out),
+                         sc, static_cast<const scalar_t*>(input), hidden_size, in_row_stride, out_row_stride,
+                         scale_row_stride, scale_group_stride, eps);
+    };
+    uint8_t* sb = static_cast<uint8_t*>(scales);
+    float* sf = static_cast<float*>(scales);
+    if (scale_elem_size == 1) {
+      if (group_size == 128) launch(per_token_group_fp8_quant_ue8m0_kernel<scalar_t, uint8_t, 16>, sb);
+      else launch(per_token_group_fp8_quant_ue8m0_kernel<scalar_t, uint8_t, 4>, sb);
+    } else {
+      if (group_size == 128) launch(per_token_group_fp8_quant_ue8m0_kernel<scalar_t, float, 16>, sf);
+      else launch(per_token_group_fp8_quant_ue8m0_kernel<scalar_t, float, 4>, sf);
+    }
+    return check_launch("per_token_group_fp8_quant(ue8m0)");
   });
 }
 

@@ -450,6 +450,36 @@ void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tens
   TORCH_CHECK(a.scalar_type() == b.scalar_type() && (is_i8 || a.scalar_type() == at::kFloat8_e4m3fn),
               "cutlass_scaled_mm: a and b must both be int8, both float8_e4m3fn or both float4_e2m1fn_x2");
   const int64_t m = a.size(0), k = a.size(1), n = b.size(1);
+  if (a_scales.scalar_type() == at::kFloat8_e8m0fnu || b_scales.scalar_type() == at::kFloat8_e8m0fnu) {
+    // E8M0-scaled fp8 (fp8_e8m0_gemm.hip); the shape of a_scales chooses the form: [m, k / 128] + [k / 128,
+    // ceil(n / 128)] (block, any strides) or [m, k / 32] + [k / 32, n] (MX, K groups contiguous)
+    TORCH_CHECK(!is_i8 && a_scales.scalar_type() == b_scales.scalar_type(),
+                "cutlass_scaled_mm: float8_e8m0fnu scales need float8_e4m3fn operands and E8M0 on both sides");
+    TORCH_CHECK(k % 128 == 0, "cutlass_scaled_mm: E8M0 scales need k % 128 == 0");
+    TORCH_CHECK(a_scales.dim() == 2 && b_scales.dim() == 2 && a_scales.size(0) == m);
+    const bool block = a_scales.size(1) == k / 128 && b_scales.size(0) == k / 128 && b_scales.size(1) == (n + 127) / 128;
+    const bool mx = a_scales.size(1) == k / 32 && b_scales.size(0) == k / 32 && b_scales.size(1) == n &&
+                    a_scales.stride(1) == 1 && b_scales.stride(0) == 1;
+    TORCH_CHECK(block || mx,
+                "cutlass_scaled_mm: E8M0 scales must be [m, k / 128] and [k / 128, ceil(n / 128)], or [m, k / 32] and "
+                "[k / 32, n] contiguous along the K groups");
+    const bool has_bias = bias.has_value() && bias->defined();
+    if (has_bias) {
+      TORCH_CHECK(bias->numel() == n && bias->is_contiguous() && bias->dim() == 1 &&
+                  bias->scalar_type() == out.scalar_type());
+    }
+    Guard g(a);
+    Tensor ws;   // slabs of a K split, for the kernel the router takes at this shape
+    if (const int64_t elems = mi355x_scaled_mm_fp8_e8m0_workspace_elems((int)m, (int)n, (int)k))
+      ws = at::empty({elems}, out.options().dtype(at::kFloat));
+    ok(mi355x_scaled_mm_fp8_e8m0(out.data_ptr(), a.data_ptr(), b.data_ptr(), a_scales.data_ptr(), a_scales.stride(0),
+                                 a_scales.stride(1), b_scales.data_ptr(), b_scales.stride(0), b_scales.stride(1),
+                                 has_bias ? bias->data_ptr() : nullptr, ws.defined() ? ws.data_ptr<float>() : nullptr,
+                                 ws.defined() ? ws.numel() : 0, m, n, k, block ? 128 : 32, a.stride(0), b.stride(1),
+                                 out.stride(0), dt(out), stream_of(a)),
+       "cutlass_scaled_mm");
+    return;
+  }
   TORCH_CHECK(a_scales.scalar_type() == at::kFloat && b_scales.scalar_type() == at::kFloat);
   if (bias.has_value() && bias->defined()) {
     TORCH_CHECK(bias->numel() == n && bias->is_contiguous() && bias->dim() == 1 &&
@@ -573,16 +603,25 @@ void dynamic_per_token_scaled_fp8_quant(Tensor& out, const Tensor& input, Tensor
 // "column-major scales" included).  fp8_min / fp8_max must be the e4m3fn range the kernel saturates to.
 void per_token_group_fp8_quant(const Tensor& input, Tensor& output_q, Tensor& output_s, int64_t group_size,
                                double eps, double fp8_min, double fp8_max, bool scale_ue8m0) {
-  TORCH_CHECK(!scale_ue8m0, "per_token_group_fp8_quant: UE8M0 scales are not implemented");
   TORCH_CHECK(fp8_max == 448.0 && fp8_min == -448.0, "per_token_group_fp8_quant: e4m3fn range (+-448) only");
   TORCH_CHECK(input.dim() == 2 && output_q.dim() == 2 && output_s.dim() == 2 && input.stride(1) == 1 &&
                   output_q.stride(1) == 1 && output_q.sizes() == input.sizes(),
               "per_token_group_fp8_quant: 2-D tensors with a contiguous last dimension");
   check_fp8(output_q);
-  TORCH_CHECK(output_s.scalar_type() == at::kFloat && output_s.size(0) == input.size(0) && group_size > 0 &&
-                  output_s.size(1) * group_size == input.size(1),
-              "per_token_group_fp8_quant: output_s must be float32 [tokens, hidden / group_size]");
+  const bool byte_s = output_s.element_size() == 1;   // float8_e8m0fnu / uint8: the scale bytes themselves
+  TORCH_CHECK((output_s.scalar_type() == at::kFloat || (byte_s && scale_ue8m0)) && output_s.size(0) == input.size(0) &&
+                  group_size > 0 && output_s.size(1) * group_size == input.size(1),
+              "per_token_group_fp8_quant: output_s must be float32 (or, with scale_ue8m0, one byte per scale) "
+              "[tokens, hidden / group_size]");
   Guard g(input);
+  if (scale_ue8m0) {
+    ok(mi355x_per_token_group_fp8_quant_ue8m0(output_q.data_ptr(), output_s.data_ptr(), byte_s ? 1 : 4,
+                                              input.data_ptr(), input.size(0), input.size(1), (int)group_size,
+                                              input.stride(0), output_q.stride(0), output_s.stride(0),
+                                              output_s.stride(1), (float)eps, dt(input), stream_of(input)),
+       "per_token_group_fp8_quant");
+    return;
+  }
   ok(mi355x_per_token_group_fp8_quant(output_q.data_ptr(), output_s.data_ptr<float>(), input.data_ptr(),
                                       input.size(0), input.size(1), (int)group_size, input.stride(0),
                                       output_q.stride(0), output_s.stride(0), output_s.stride(1), (float)eps,

@@ -110,16 +110,41 @@ def apply_fp8_block(x: torch.Tensor, weight: torch.Tensor, weight_scale_inv: tor
                     bias: Optional[torch.Tensor]) -> torch.Tensor:
     """Linear on a block-quantised fp8 checkpoint layer (weight_block_size = [128, 128]): `weight` e4m3fn [n, k],
     `weight_scale_inv` float32 [ceil(n / 128), k / 128].  The activations are quantised per token and 128-wide group
-    on the fly; weight and scales go to the GEMM as transposed views, without a copy."""
+    on the fly; weight and scales go to the GEMM as transposed views, without a copy.  A `weight_scale_inv` of E8M0
+    bytes (uint8 / float8_e8m0fnu: `scale_fmt: ue8m0`) takes the E8M0-scaled GEMM, the activations quantised with
+    power-of-two scales to match."""
     reshaped_x = x.reshape(-1, x.shape[-1])
     n = weight.shape[0]
-    q, s = ops.per_token_group_quant_fp8(reshaped_x, 128)
+    if weight_scale_inv.dtype in (torch.uint8, torch.float8_e8m0fnu):
+        weight_scale_inv = weight_scale_inv.view(torch.float8_e8m0fnu)
+        q, s = ops.per_token_group_quant_fp8(reshaped_x, 128, scale_ue8m0=True, scale_dtype=torch.float8_e8m0fnu)
+    else:
+        q, s = ops.per_token_group_quant_fp8(reshaped_x, 128)
     out = torch.empty((reshaped_x.shape[0], n), dtype=x.dtype, device=x.device)
     ops.cutlass_scaled_mm(out, q, weight.t(), s, weight_scale_inv.t(), bias)
     return out.reshape(x.shape[:-1] + (n,))
 
 
 def apply_fp8_block_fake(x, weight, weight_scale_inv, bias):
+    return torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=x.dtype, device=x.device)
+
+
+def apply_mxfp8(x: torch.Tensor, weight: torch.Tensor, weight_scale: torch.Tensor,
+                bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """Linear on an OCP MXFP8 checkpoint layer: `weight` e4m3fn [n, k], `weight_scale` [n, k / 32] E8M0 bytes as uint8
+    or float8_e8m0fnu.  The activations are quantised per token and 32-wide group with power-of-two scales on the fly;
+    weight and scales go to the GEMM as transposed views, without a copy."""
+    reshaped_x = x.reshape(-1, x.shape[-1])
+    n = weight.shape[0]
+    if weight_scale.dtype == torch.uint8:
+        weight_scale = weight_scale.view(torch.float8_e8m0fnu)
+    q, s = ops.per_token_group_quant_fp8(reshaped_x, 32, scale_ue8m0=True, scale_dtype=torch.float8_e8m0fnu)
+    out = torch.empty((reshaped_x.shape[0], n), dtype=x.dtype, device=x.device)
+    ops.cutlass_scaled_mm(out, q, weight.t(), s, weight_scale.t(), bias)
+    return out.reshape(x.shape[:-1] + (n,))
+
+
+def apply_mxfp8_fake(x, weight, weight_scale, bias):
     return torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=x.dtype, device=x.device)
 
 
